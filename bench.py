@@ -6,7 +6,13 @@ node, weak scaling (fixed per-GPU batch), synthetic data, random-init
 weights.  Launched directly (N=1) or via torch.distributed.run with one
 rank per GPU over RCCL.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times K steps and prints one JSON line.
+--dump-outputs DIR also writes what the last timed step computed (loss,
+logits, updated parameters) as DIR/<name>.npy so two builds can be
+compared output for output; the seed fixes weights and data, so the
+same arguments give the same inputs on every run.
 """
 from __future__ import annotations
 
@@ -16,6 +22,39 @@ import os
 import time
 
 import torch
+
+# --dump-outputs caps: elements per sampled array / per parameter tensor
+# (float32, so the three files together stay far below 64 MB)
+_DUMP_MAX_ELEMS = 1 << 22
+_DUMP_PER_PARAM = 4096
+_DUMP_SEED = 20240917
+
+
+def _sample(t, max_elems, gen):
+    """Whole tensor as flat float32 numpy, or a fixed seeded sample of it."""
+    flat = t.detach().reshape(-1)
+    if flat.numel() > max_elems:
+        idx = torch.randint(0, flat.numel(), (max_elems,), generator=gen)
+        flat = flat[idx.to(flat.device)]
+    return flat.float().cpu().numpy()
+
+
+def dump_outputs(out_dir, loss, logits, state, write):
+    """Write the last timed step's results as float32 .npy files.  The
+    sample indices depend only on the shapes, so they match across runs."""
+    import numpy as np
+    gen = torch.Generator().manual_seed(_DUMP_SEED)
+    arrays = {
+        "loss": loss.detach().float().reshape(1).cpu().numpy(),
+        "logits": _sample(logits, _DUMP_MAX_ELEMS, gen),
+        "params": np.concatenate([_sample(state[k], _DUMP_PER_PARAM, gen)
+                                  for k in sorted(state)]),
+    }
+    if not write:
+        return
+    os.makedirs(out_dir, exist_ok=True)
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
 
 
 def main():
@@ -34,6 +73,14 @@ def main():
                     help="tiny CPU run for plumbing checks")
     ap.add_argument("--tunableop", action="store_true",
                     help="autotune hipBLASLt GEMM algo selection during warmup")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="after the timed steps write the last step's loss, "
+                         "logits and updated parameters (seeded samples of "
+                         "the large ones) to DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary measurement; bench.py has "
+                         "none beyond the headline figure today, so this "
+                         "changes nothing yet")
     args = ap.parse_args()
 
     if args.tunableop:
@@ -91,8 +138,14 @@ def main():
     ids = torch.randint(0, vocab, (args.batch, args.seq), device=dev)
     labels = torch.randint(0, vocab, (args.batch, args.seq), device=dev)
 
-    def step():
-        loss = loss_fn(wrapped(ids), labels)
+    kept = {}
+
+    def step(keep=False):
+        logits = wrapped(ids)
+        loss = loss_fn(logits, labels)
+        if keep:
+            kept["logits"] = logits.detach()
+        del logits
         loss.backward()
         opt.step()
         opt.clear_grad()
@@ -111,8 +164,8 @@ def main():
     if on_gpu:
         torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        loss = step()
+    for i in range(args.steps):
+        loss = step(keep=args.dump_outputs is not None and i == args.steps - 1)
     if on_gpu:
         torch.cuda.synchronize()
     if world > 1:
@@ -124,6 +177,11 @@ def main():
         t = torch.tensor([elapsed], device=dev if on_gpu else "cpu")
         paddle.distributed.all_reduce(t, op=paddle.distributed.ReduceOp.MAX)
         elapsed = float(t.item())
+
+    if args.dump_outputs is not None:
+        # state_dict() gathers sharded parameters, so every rank takes part
+        dump_outputs(args.dump_outputs, loss, kept.pop("logits"),
+                     wrapped.state_dict(), write=rank == 0)
 
     n_gpus = world if world > 1 else (1 if on_gpu else 0) or 1
     total_tokens = args.batch * args.seq * args.steps * n_gpus

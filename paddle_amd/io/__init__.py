@@ -202,8 +202,11 @@ class DataLoader:
             self._loader = tud.DataLoader(dataset, batch_sampler=self.batch_sampler, **kwargs)
 
     def __iter__(self):
+        # batches follow paddle's default device (set_device("cpu") on a GPU
+        # box keeps them on the host, where the model's parameters are)
+        from ..framework import get_default_device
         dev = None
-        if torch.cuda.is_available():
+        if torch.cuda.is_available() and get_default_device().type == "cuda":
             dev = torch.device("cuda", torch.cuda.current_device())
         for batch in self._loader:
             if dev is not None:

@@ -77,7 +77,10 @@ def test_launch_cli_single_proc(tmp_path):
         "assert t.tolist() == [2.0, 2.0]\n"
         "print('rank', os.environ['RANK'], 'ok')\n" % REPO)
     env = dict(os.environ)
-    env["CUDA_VISIBLE_DEVICES"] = ""
+    # ROCm ignores CUDA_VISIBLE_DEVICES: hide the GPUs properly so both
+    # ranks take the gloo path on a GPU box too (as dist_util.run_dist does)
+    for var in ("CUDA_VISIBLE_DEVICES", "HIP_VISIBLE_DEVICES", "ROCR_VISIBLE_DEVICES"):
+        env[var] = ""
     env["PYTHONPATH"] = REPO
     from dist_util import free_port
     r = subprocess.run([sys.executable, "-m", "paddle_amd.distributed.launch",

@@ -112,9 +112,17 @@ tl = paddle.jit.load(r"{d}/model")
 io = torch.load(r"{d}/io.pt", weights_only=False)
 assert (tl(io["x"]) - io["ref"]).abs().max().item() < 1e-5
 '''
+    import os
+    from dist_util import REPO
+    env = dict(os.environ)
+    env["PYTHONPATH"] = REPO + os.pathsep + env.get("PYTHONPATH", "")
+    # a CPU test: hide the GPUs (ROCm ignores CUDA_VISIBLE_DEVICES) so the
+    # fresh processes build the model where the CPU inputs live
+    for var in ("CUDA_VISIBLE_DEVICES", "HIP_VISIBLE_DEVICES", "ROCR_VISIBLE_DEVICES"):
+        env[var] = ""
     for code in (save_code, load_code):
         r = subprocess.run([sys.executable, "-c", code], capture_output=True,
-                           text=True)
+                           text=True, env=env)
         assert r.returncode == 0, r.stderr[-2000:]
 
 
