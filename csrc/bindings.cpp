@@ -37,8 +37,10 @@ int dt_of(const Tensor& t) {
   switch (t.scalar_type()) {
     case torch::kBFloat16: return pa::kBF16;
     case torch::kFloat: return pa::kF32;
-    case torch::kHalf: return pa::kF16;
-    default: TORCH_CHECK(false, "unsupported dtype ", t.scalar_type());
+    // no kernel template reads fp16 (pa::kF16 is reserved): the launchers
+    // treat "not bf16" as fp32, so a half tensor must never get this far
+    default: TORCH_CHECK(false, "unsupported dtype ", t.scalar_type(),
+                         " (native kernels take bfloat16 or float32)");
   }
   return -1;
 }
@@ -46,12 +48,42 @@ int dt_of(const Tensor& t) {
 #define CHECK_IN(t) \
   TORCH_CHECK(t.is_cuda() && t.is_contiguous(), #t " must be contiguous GPU tensor")
 
+// operand handed to a kernel next to x: contiguous GPU tensor of x's dtype
+// (the kernels reinterpret every pointer in the dtype of x)
+#define CHECK_LIKE(t, x)                                                      \
+  TORCH_CHECK(t.is_cuda() && t.is_contiguous() &&                             \
+              t.scalar_type() == x.scalar_type(),                             \
+              #t " must be a contiguous GPU tensor with the dtype of " #x)
+// same, and the same number of elements (dy, residual, ...)
+#define CHECK_SAME(t, x)                                                      \
+  do { CHECK_LIKE(t, x);                                                      \
+       TORCH_CHECK(t.numel() == x.numel(), #t " must have the size of " #x);  \
+  } while (0)
+// per-column parameter (weight / bias): dtype of x, d elements
+#define CHECK_VEC(t, x, d)                                                    \
+  do { CHECK_LIKE(t, x);                                                      \
+       TORCH_CHECK(t.numel() == (d), #t " must have ", (d), " elements");     \
+  } while (0)
+// saved fp32 row statistics
+#define CHECK_STAT(t, n)                                                      \
+  TORCH_CHECK(t.is_cuda() && t.is_contiguous() &&                             \
+              t.scalar_type() == torch::kFloat && t.numel() == (n),           \
+              #t " must be a contiguous fp32 GPU tensor with ", (n), " elements")
+
+// last-dim contract of the 8-wide row kernels
+static void check_rows(const Tensor& x, const char* op) {
+  TORCH_CHECK(x.dim() >= 1 && x.numel() > 0, op, ": empty input");
+  TORCH_CHECK(x.size(-1) % 8 == 0, op, ": D must be a multiple of 8");
+}
+
 // ---- norms ----------------------------------------------------------------
 std::vector<Tensor> layer_norm_fwd(const Tensor& x, const Tensor& w,
                                    const c10::optional<Tensor>& b, double eps) {
-  CHECK_IN(x); CHECK_IN(w);
+  CHECK_IN(x);
+  check_rows(x, "layer_norm");
   int64_t d = x.size(-1), n = x.numel() / d;
-  TORCH_CHECK(d % 8 == 0, "layer_norm: D must be multiple of 8");
+  CHECK_VEC(w, x, d);
+  if (b.has_value()) CHECK_VEC((*b), x, d);
   auto y = torch::empty_like(x);
   auto mean = torch::empty({n}, x.options().dtype(torch::kFloat));
   auto rstd = torch::empty({n}, x.options().dtype(torch::kFloat));
@@ -66,8 +98,11 @@ std::vector<Tensor> layer_norm_fwd(const Tensor& x, const Tensor& w,
 std::vector<Tensor> layer_norm_bwd(const Tensor& dy, const Tensor& x,
                                    const Tensor& w, const Tensor& mean,
                                    const Tensor& rstd, bool has_bias) {
-  CHECK_IN(dy); CHECK_IN(x); CHECK_IN(w);
+  CHECK_IN(x);
+  check_rows(x, "layer_norm_bwd");
   int64_t d = x.size(-1), n = x.numel() / d;
+  CHECK_SAME(dy, x); CHECK_VEC(w, x, d);
+  CHECK_STAT(mean, n); CHECK_STAT(rstd, n);
   auto dx = torch::empty_like(x);
   auto dw = torch::zeros({d}, x.options().dtype(torch::kFloat));
   auto db = torch::zeros({d}, x.options().dtype(torch::kFloat));
@@ -80,21 +115,24 @@ std::vector<Tensor> layer_norm_bwd(const Tensor& dy, const Tensor& x,
                           mean.const_data_ptr<float>(), rstd.const_data_ptr<float>(),
                           dw.mutable_data_ptr<float>(), db.mutable_data_ptr<float>(),
                           n, d, dt_of(x), cur_stream(), ws.mutable_data_ptr<float>());
-  return {dx, dw.to(x.scalar_type()), db.to(x.scalar_type())};
+  // dw/db stay fp32: the caller casts them to the parameter's dtype, which
+  // under amp O2 is fp32 next to bf16 activations
+  return {dx, dw, db};
 }
 
 std::vector<Tensor> rms_norm_fwd(const Tensor& x, const c10::optional<Tensor>& residual,
                                  const Tensor& w, double eps) {
-  CHECK_IN(x); CHECK_IN(w);
+  CHECK_IN(x);
+  check_rows(x, "rms_norm");
   int64_t d = x.size(-1), n = x.numel() / d;
-  TORCH_CHECK(d % 8 == 0, "rms_norm: D must be multiple of 8");
+  CHECK_VEC(w, x, d);
   auto y = torch::empty_like(x);
   auto rstd = torch::empty({n}, x.options().dtype(torch::kFloat));
   Tensor res_out;
   const void* resp = nullptr;
   void* res_outp = nullptr;
   if (residual.has_value()) {
-    CHECK_IN((*residual));
+    CHECK_SAME((*residual), x);
     res_out = torch::empty_like(x);
     resp = residual->const_data_ptr();
     res_outp = res_out.mutable_data_ptr();
@@ -108,8 +146,10 @@ std::vector<Tensor> rms_norm_fwd(const Tensor& x, const c10::optional<Tensor>& r
 
 std::vector<Tensor> rms_norm_bwd(const Tensor& dy, const Tensor& x, const Tensor& w,
                                  const Tensor& rstd) {
-  CHECK_IN(dy); CHECK_IN(x); CHECK_IN(w);
+  CHECK_IN(x);
+  check_rows(x, "rms_norm_bwd");
   int64_t d = x.size(-1), n = x.numel() / d;
+  CHECK_SAME(dy, x); CHECK_VEC(w, x, d); CHECK_STAT(rstd, n);
   auto dx = torch::empty_like(x);
   auto dw = torch::zeros({d}, x.options().dtype(torch::kFloat));
   pa::rms_norm_bwd_dx(dy.const_data_ptr(), x.const_data_ptr(), w.const_data_ptr(),
@@ -120,14 +160,17 @@ std::vector<Tensor> rms_norm_bwd(const Tensor& dy, const Tensor& x, const Tensor
   pa::rms_norm_bwd_dw(dy.const_data_ptr(), x.const_data_ptr(),
                       rstd.const_data_ptr<float>(), dw.mutable_data_ptr<float>(),
                       n, d, dt_of(x), cur_stream(), ws.mutable_data_ptr<float>());
-  return {dx, dw.to(x.scalar_type())};
+  return {dx, dw};  // fp32, cast by the caller
 }
 
 // ---- cross entropy --------------------------------------------------------
 std::vector<Tensor> softmax_ce_fwd(const Tensor& logits, const Tensor& labels,
                                    int64_t ignore_index) {
   CHECK_IN(logits); CHECK_IN(labels);
+  TORCH_CHECK(logits.dim() >= 1 && logits.numel() > 0, "softmax_ce: empty logits");
   int64_t v = logits.size(-1), n = logits.numel() / v;
+  TORCH_CHECK(labels.scalar_type() == torch::kLong && labels.numel() == n,
+              "softmax_ce: labels must be int64 with one entry per row");
   auto loss = torch::empty({n}, logits.options().dtype(torch::kFloat));
   auto lse = torch::empty({n}, logits.options().dtype(torch::kFloat));
   pa::softmax_ce_fwd(logits.const_data_ptr(), labels.const_data_ptr<int64_t>(),
@@ -138,8 +181,12 @@ std::vector<Tensor> softmax_ce_fwd(const Tensor& logits, const Tensor& labels,
 
 Tensor softmax_ce_bwd(const Tensor& dloss, const Tensor& logits,
                       const Tensor& labels, const Tensor& lse, int64_t ignore_index) {
-  CHECK_IN(logits);
+  CHECK_IN(logits); CHECK_IN(labels);
+  TORCH_CHECK(logits.dim() >= 1 && logits.numel() > 0, "softmax_ce_bwd: empty logits");
   int64_t v = logits.size(-1), n = logits.numel() / v;
+  TORCH_CHECK(labels.scalar_type() == torch::kLong && labels.numel() == n,
+              "softmax_ce_bwd: labels must be int64 with one entry per row");
+  CHECK_STAT(dloss, n); CHECK_STAT(lse, n);
   auto dlogits = torch::empty_like(logits);
   pa::softmax_ce_bwd(dloss.const_data_ptr<float>(), logits.const_data_ptr(),
                      labels.const_data_ptr<int64_t>(), lse.const_data_ptr<float>(),
@@ -151,8 +198,9 @@ Tensor softmax_ce_bwd(const Tensor& dloss, const Tensor& logits,
 // ---- elementwise ----------------------------------------------------------
 Tensor bias_gelu_fwd(const Tensor& x, const c10::optional<Tensor>& bias) {
   CHECK_IN(x);
+  check_rows(x, "bias_gelu");
   int64_t d = x.size(-1), n = x.numel() / d;
-  TORCH_CHECK(d % 8 == 0);
+  if (bias.has_value()) CHECK_VEC((*bias), x, d);
   auto y = torch::empty_like(x);
   pa::bias_gelu_fwd(x.const_data_ptr(), bias.has_value() ? bias->const_data_ptr() : nullptr,
                     y.mutable_data_ptr(), n, d, dt_of(x), cur_stream());
@@ -160,8 +208,11 @@ Tensor bias_gelu_fwd(const Tensor& x, const c10::optional<Tensor>& bias) {
 }
 
 Tensor bias_gelu_bwd(const Tensor& dy, const Tensor& x, const c10::optional<Tensor>& bias) {
-  CHECK_IN(dy); CHECK_IN(x);
+  CHECK_IN(x);
+  check_rows(x, "bias_gelu_bwd");
   int64_t d = x.size(-1), n = x.numel() / d;
+  CHECK_SAME(dy, x);
+  if (bias.has_value()) CHECK_VEC((*bias), x, d);
   auto dx = torch::empty_like(x);
   pa::bias_gelu_bwd(dy.const_data_ptr(), x.const_data_ptr(),
                     bias.has_value() ? bias->const_data_ptr() : nullptr,
@@ -171,8 +222,9 @@ Tensor bias_gelu_bwd(const Tensor& dy, const Tensor& x, const c10::optional<Tens
 
 Tensor swiglu_fwd(const Tensor& x) {
   CHECK_IN(x);
+  TORCH_CHECK(x.dim() >= 1 && x.numel() > 0, "swiglu: empty input");
   int64_t d2 = x.size(-1), n = x.numel() / d2, d = d2 / 2;
-  TORCH_CHECK(d % 8 == 0);
+  TORCH_CHECK(d2 % 16 == 0, "swiglu: last dim must be a multiple of 16");
   auto sizes = x.sizes().vec();
   sizes.back() = d;
   auto y = torch::empty(sizes, x.options());
@@ -181,8 +233,12 @@ Tensor swiglu_fwd(const Tensor& x) {
 }
 
 Tensor swiglu_bwd(const Tensor& dy, const Tensor& x) {
-  CHECK_IN(dy); CHECK_IN(x);
+  CHECK_IN(x);
+  TORCH_CHECK(x.dim() >= 1 && x.numel() > 0, "swiglu_bwd: empty input");
   int64_t d2 = x.size(-1), n = x.numel() / d2, d = d2 / 2;
+  TORCH_CHECK(d2 % 16 == 0, "swiglu_bwd: last dim must be a multiple of 16");
+  CHECK_LIKE(dy, x);
+  TORCH_CHECK(dy.numel() == n * d, "swiglu_bwd: dy must have half the size of x");
   auto dx = torch::empty_like(x);
   pa::swiglu_bwd(dy.const_data_ptr(), x.const_data_ptr(), dx.mutable_data_ptr(),
                  n, d, dt_of(x), cur_stream());
@@ -194,7 +250,15 @@ Tensor rope_fwd(const Tensor& x, const Tensor& cos_t, const Tensor& sin_t,
   CHECK_IN(x); CHECK_IN(cos_t); CHECK_IN(sin_t);
   TORCH_CHECK(x.dim() == 4, "rope expects [B,S,H,D]");
   int64_t b = x.size(0), sl = x.size(1), h = x.size(2), dh = x.size(3);
-  TORCH_CHECK((dh / 2) % 4 == 0, "rope: head_dim/2 must be multiple of 4");
+  TORCH_CHECK(dh % 2 == 0 && (dh / 2) % 4 == 0 && x.numel() > 0,
+              "rope: head_dim/2 must be multiple of 4");
+  TORCH_CHECK(pos_offset >= 0, "rope: pos_offset must be >= 0");
+  TORCH_CHECK(cos_t.scalar_type() == torch::kFloat &&
+              sin_t.scalar_type() == torch::kFloat &&
+              cos_t.dim() == 2 && sin_t.dim() == 2 &&
+              cos_t.size(1) == dh / 2 && sin_t.size(1) == dh / 2 &&
+              cos_t.size(0) >= sl + pos_offset && sin_t.size(0) >= sl + pos_offset,
+              "rope: cos/sin must be fp32 [>= seq_len + pos_offset, head_dim/2]");
   auto y = torch::empty_like(x);
   pa::rope_fwd(x.const_data_ptr(), cos_t.const_data_ptr<float>(),
                sin_t.const_data_ptr<float>(), y.mutable_data_ptr(), b, sl, h, dh,
@@ -204,6 +268,7 @@ Tensor rope_fwd(const Tensor& x, const Tensor& cos_t, const Tensor& sin_t,
 
 Tensor colsum(const Tensor& x) {
   CHECK_IN(x);
+  TORCH_CHECK(x.dim() >= 1 && x.numel() > 0, "colsum: empty input");
   int64_t d = x.size(-1), n = x.numel() / d;
   auto out = torch::zeros({d}, x.options().dtype(torch::kFloat));
   pa::colsum(x.const_data_ptr(), out.mutable_data_ptr<float>(), n, d, dt_of(x),
@@ -234,9 +299,20 @@ void adamw(Tensor& master, c10::optional<Tensor> param_out, const Tensor& grad,
            double grad_scale) {
   CHECK_IN(master); CHECK_IN(grad); CHECK_IN(m); CHECK_IN(v);
   int64_t numel = master.numel();
+  TORCH_CHECK(master.scalar_type() == torch::kFloat &&
+              m.scalar_type() == torch::kFloat && v.scalar_type() == torch::kFloat,
+              "adamw: master, m and v must be fp32");
+  TORCH_CHECK(grad.numel() == numel && m.numel() == numel && v.numel() == numel,
+              "adamw: grad, m and v must have the size of master");
   bool bf16out = false;
   void* pout = nullptr;
   if (param_out.has_value()) {
+    TORCH_CHECK(param_out->is_cuda() && param_out->is_contiguous() &&
+                param_out->numel() == numel &&
+                (param_out->scalar_type() == torch::kBFloat16 ||
+                 param_out->scalar_type() == torch::kFloat),
+                "adamw: param_out must be a contiguous bf16 or fp32 GPU tensor "
+                "with the size of master");
     bf16out = param_out->scalar_type() == torch::kBFloat16;
     pout = param_out->mutable_data_ptr();
   }
@@ -441,6 +517,10 @@ Tensor fa_dropout_mask(int64_t b, int64_t h, int64_t sq, int64_t skv,
 std::vector<Tensor> dropout_add_fwd(const Tensor& x, const c10::optional<Tensor>& residual,
                                     double p, int64_t seed, int64_t offset) {
   CHECK_IN(x);
+  TORCH_CHECK(x.numel() > 0 && x.numel() % 8 == 0,
+              "dropout_add: numel must be a multiple of 8");
+  TORCH_CHECK(p >= 0.0 && p < 1.0, "dropout_add: p must be in [0, 1)");
+  if (residual.has_value()) CHECK_SAME((*residual), x);
   auto y = torch::empty_like(x);
   Tensor mask;
   uint8_t* maskp = nullptr;
@@ -458,6 +538,11 @@ std::vector<Tensor> dropout_add_fwd(const Tensor& x, const c10::optional<Tensor>
 
 Tensor dropout_add_bwd(const Tensor& dy, const Tensor& mask, double p) {
   CHECK_IN(dy); CHECK_IN(mask);
+  TORCH_CHECK(dy.numel() > 0 && dy.numel() % 8 == 0,
+              "dropout_add_bwd: numel must be a multiple of 8");
+  TORCH_CHECK(mask.scalar_type() == torch::kUInt8 && mask.numel() == dy.numel(),
+              "dropout_add_bwd: mask must be uint8 with the size of dy");
+  TORCH_CHECK(p >= 0.0 && p < 1.0, "dropout_add_bwd: p must be in [0, 1)");
   auto dx = torch::empty_like(dy);
   pa::dropout_add_bwd(dy.const_data_ptr(), mask.const_data_ptr<uint8_t>(),
                       dx.mutable_data_ptr(), dy.numel(), (float)p, dt_of(dy),
@@ -469,9 +554,11 @@ Tensor dropout_add_bwd(const Tensor& dy, const Tensor& mask, double p) {
 Tensor embedding_fwd(const Tensor& table, const Tensor& ids_in, int64_t padding_idx) {
   CHECK_IN(table);
   TORCH_CHECK(ids_in.is_cuda(), "ids must be on GPU");
+  TORCH_CHECK(ids_in.scalar_type() == torch::kLong, "embedding: ids must be int64");
+  TORCH_CHECK(table.dim() == 2 && table.numel() > 0, "embedding: table must be [vocab, D]");
   auto ids = ids_in.contiguous();
   int64_t vocab = table.size(0), d = table.size(1), n = ids.numel();
-  TORCH_CHECK(d % 8 == 0);
+  TORCH_CHECK(d % 8 == 0, "embedding: D must be a multiple of 8");
   auto sizes = ids.sizes().vec();
   sizes.push_back(d);
   auto out = torch::empty(sizes, table.options());
@@ -485,8 +572,12 @@ Tensor embedding_bwd(const Tensor& dout, const Tensor& ids_in, int64_t vocab,
                      int64_t padding_idx) {
   CHECK_IN(dout);
   TORCH_CHECK(ids_in.is_cuda(), "ids must be on GPU");
+  TORCH_CHECK(ids_in.scalar_type() == torch::kLong, "embedding_bwd: ids must be int64");
   auto ids = ids_in.contiguous();
+  TORCH_CHECK(dout.dim() >= 1 && dout.numel() > 0 && vocab > 0, "embedding_bwd: empty input");
   int64_t d = dout.size(-1), n = ids.numel();
+  TORCH_CHECK(d % 8 == 0, "embedding_bwd: D must be a multiple of 8");
+  TORCH_CHECK(dout.numel() == n * d, "embedding_bwd: dout must be [ids..., D]");
   auto dtable = torch::zeros({vocab, d}, dout.options().dtype(torch::kFloat));
   pa::embedding_bwd(dout.const_data_ptr(), ids.const_data_ptr<int64_t>(),
                     dtable.mutable_data_ptr<float>(), n, d, vocab, padding_idx,

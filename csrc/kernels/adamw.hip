@@ -40,6 +40,9 @@ __global__ void adamw_kernel(float* __restrict__ master, void* __restrict__ para
     float vo[4] = {vv.x, vv.y, vv.z, vv.w};
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
+      // keep (1-beta)*g as written: -ffast-math otherwise evaluates it as
+      // g - beta*g, which costs an ulp of g (not of (1-beta)*g) per step
+#pragma clang fp reassociate(off)
       // decoupled weight decay (AdamW): p *= (1 - lr*wd)
       p[k] -= lr * wd * p[k];
       mo[k] = beta1 * mo[k] + (1.f - beta1) * g[k];
@@ -62,6 +65,7 @@ __global__ void adamw_kernel(float* __restrict__ master, void* __restrict__ para
   }
   for (int64_t i = numel4 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < numel;
        i += (int64_t)gridDim.x * blockDim.x) {
+#pragma clang fp reassociate(off)
     float g = (GDT == kBF16) ? bf2f(((const short*)grad)[i]) * gscale
                              : ((const float*)grad)[i] * gscale;
     float p = master[i];

@@ -49,13 +49,25 @@ template <> struct VIO2<kF32> {
   }
 };
 
-// merge two (max, sumexp) pairs
+// Running maximum of a lane that has seen nothing yet.  It is the largest
+// finite negative float, not -inf: a -inf logit (a banned token) that arrives
+// while the maximum is still "empty" then gives x - m = -inf and adds
+// exp(-inf) = 0, where -inf - -inf would be NaN.  Testing for infinity
+// instead does not work in this tree: it is built with -ffast-math, which
+// lets the compiler fold such a test away (bit-pattern compares included).
+#define LSE_EMPTY (-3.402823466e+38f)
+
+// one online-softmax step
+__device__ __forceinline__ void lse_step(float& m, float& l, float x) {
+  if (x > m) { l *= __expf(m - x); m = x; }
+  l += __expf(x - m);
+}
+
+// merge two (max, sumexp) pairs; m - mn is <= 0, finite or -inf, never NaN
 __device__ __forceinline__ void lse_merge(float& m, float& l, float m2, float l2) {
   float mn = fmaxf(m, m2);
-  // guard -inf - -inf
   float a = (m == mn) ? l : l * __expf(m - mn);
   float b = (m2 == mn) ? l2 : l2 * __expf(m2 - mn);
-  if (m == -INFINITY && m2 == -INFINITY) { l = 0.f; m = -INFINITY; return; }
   l = a + b;
   m = mn;
 }
@@ -68,24 +80,18 @@ __global__ void ce_fwd_kernel(const void* __restrict__ logits,
   __shared__ float red_m[4], red_l[4];
   for (int64_t row = blockIdx.x; row < n; row += gridDim.x) {
     const int64_t base = row * v;
-    float m = -INFINITY, l = 0.f;
+    float m = LSE_EMPTY, l = 0.f;
     int64_t i = threadIdx.x * 8;
     const int64_t v8 = v & ~7LL;
     for (; i < v8; i += blockDim.x * 8) {
       float f[8];
       VIO2<DT>::load8(logits, base + i, f);
 #pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        float x = f[k];
-        if (x > m) { l *= __expf(m - x); m = x; }
-        l += __expf(x - m);
-      }
+      for (int k = 0; k < 8; ++k) lse_step(m, l, f[k]);
     }
     // tail
     for (int64_t j = v8 + threadIdx.x; j < v; j += blockDim.x) {
-      float x = VIO2<DT>::load1(logits, base + j);
-      if (x > m) { l *= __expf(m - x); m = x; }
-      l += __expf(x - m);
+      lse_step(m, l, VIO2<DT>::load1(logits, base + j));
     }
     // wave reduce
 #pragma unroll
@@ -104,7 +110,9 @@ __global__ void ce_fwd_kernel(const void* __restrict__ logits,
     if (threadIdx.x == 0) {
       int64_t lab = labels[row];
       lse_out[row] = lse;
-      if (lab == ignore_index) {
+      // a label outside [0, v) is never dereferenced: like ignore_index it
+      // contributes zero loss (and zero gradient in ce_bwd_kernel)
+      if (lab == ignore_index || lab < 0 || lab >= v) {
         loss[row] = 0.f;
       } else {
         float xl = VIO2<DT>::load1(logits, base + lab);
@@ -124,7 +132,7 @@ __global__ void ce_bwd_kernel(const float* __restrict__ dloss,
   for (int64_t row = blockIdx.x; row < n; row += gridDim.x) {
     const int64_t base = row * v;
     const int64_t lab = labels[row];
-    const float g = (lab == ignore_index) ? 0.f : dloss[row];
+    const float g = (lab == ignore_index || lab < 0 || lab >= v) ? 0.f : dloss[row];
     const float ls = lse[row];
     const int64_t v8 = v & ~7LL;
     int64_t i = threadIdx.x * 8;

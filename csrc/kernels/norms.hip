@@ -8,7 +8,9 @@
 //
 // Reference behavior parity: paddle/phi/kernels/gpu/layer_norm_kernel.cu
 // (LayerNormFwdWithWelford) and rms_norm_kernel.cu (cuApplyRMSNorm) --
-// re-derived, not ported.
+// re-derived, not ported.  LayerNorm's variance uses shifted single-pass
+// moments (see ln_fwd_kernel), not Welford merging; both are robust to a
+// row mean far from zero.
 #include "common.h"
 #include "api.h"
 
@@ -67,21 +69,46 @@ __global__ void ln_fwd_kernel(const void* __restrict__ x, const void* __restrict
                               const void* __restrict__ b, void* __restrict__ y,
                               float* __restrict__ mean_out, float* __restrict__ rstd_out,
                               int64_t n, int64_t d, float eps) {
-  __shared__ float red[8];
+  __shared__ float red[12];
   for (int64_t row = blockIdx.x; row < n; row += gridDim.x) {
     const int64_t base = row * d;
-    float sum = 0.f, sumsq = 0.f;
+    // Shifted moments: the variance comes from sum(x-K) and sum((x-K)^2).
+    // E[x^2] - mu^2 on the raw values cancels in fp32 once |mu| >> sigma
+    // (var clamps to 0 near mu = 3000*sigma); after the shift the same
+    // identity only cancels against (mu - K)^2.  K is the mean of the row's
+    // first 8 elements (one broadcast load per row, d % 8 == 0), so that one
+    // outlier in column 0 moves K by an eighth of its size only.  A row whose
+    // first 8 elements all sit far from the rest (|K - mu| >> sigma) still
+    // loses log2((K-mu)^2/var) bits of the variance.
+    // The mean itself is the plain sum / d: K + mean(x-K) would round at
+    // ulp(K), which is coarse when |mu| << |K|.
+    float shift;
+    {
+      float f0[8];
+      VIO<DT>::load8(x, base, f0);
+      shift = ((f0[0] + f0[1]) + (f0[2] + f0[3]) + (f0[4] + f0[5]) + (f0[6] + f0[7])) * 0.125f;
+    }
+    float sum = 0.f, sumc = 0.f, sumsq = 0.f;
     for (int64_t i = threadIdx.x * 8; i < d; i += blockDim.x * 8) {
       float f[8];
       VIO<DT>::load8(x, base + i, f);
 #pragma unroll
-      for (int k = 0; k < 8; ++k) { sum += f[k]; sumsq += f[k] * f[k]; }
+      for (int k = 0; k < 8; ++k) {
+        // -ffast-math may otherwise fold the eight "- shift" into one
+        // "- 8*shift" after summing the raw values
+#pragma clang fp reassociate(off)
+        float c = f[k] - shift;
+        sum += f[k];
+        sumc += c;
+        sumsq += c * c;
+      }
     }
     float ts = block_reduce_256(sum, SumOp(), red, 0.f);
-    __syncthreads();
-    float tss = block_reduce_256(sumsq, SumOp(), red + 4, 0.f);
+    float tsc = block_reduce_256(sumc, SumOp(), red + 4, 0.f);
+    float tss = block_reduce_256(sumsq, SumOp(), red + 8, 0.f);
     float mu = ts / d;
-    float var = fmaxf(tss / d - mu * mu, 0.f);
+    float dmu = tsc / d;  // mean of the shifted row
+    float var = fmaxf(tss / d - dmu * dmu, 0.f);
     float rstd = rsqrtf(var + eps);
     if (threadIdx.x == 0) { mean_out[row] = mu; rstd_out[row] = rstd; }
     for (int64_t i = threadIdx.x * 8; i < d; i += blockDim.x * 8) {

@@ -27,15 +27,122 @@ def _tracing():
 
 
 # ---------------------------------------------------------------------------
+# Kernel contract (docs/KERNELS.md "kernel contract and tolerances").
+#
+# The row/elementwise kernels exist as bf16 and fp32 templates only, read
+# and write 8 elements per lane, and reinterpret every operand pointer in
+# the dtype of x.  The predicates below decide from dtypes, shapes and
+# contiguity alone -- no CUDA call -- whether a kernel may take a call;
+# anything outside the contract takes the torch composite path, which
+# works on GPU tensors too.  Per-column parameters (weight / bias, D
+# elements) of another dtype are cast to x.dtype by the caller instead,
+# so amp O2 (fp32 norm parameters, bf16 activations) stays on the kernel.
+# ---------------------------------------------------------------------------
+_NATIVE_DTYPES = (torch.bfloat16, torch.float32)
+
+
+def _kernel_ok(x, *, last_mult=1, numel_mult=1, same=(), vecs=(),
+               contiguous=()):
+    """Shared contract check.  x: the tensor whose dtype picks the kernel
+    template.  last_mult / numel_mult: divisibility of x.shape[-1] /
+    x.numel().  same: full-size operands (dtype and shape of x, or None).
+    vecs: per-column parameters (floating point, x.shape[-1] elements, or
+    None).  contiguous: tensors the op hands over without .contiguous()."""
+    if not isinstance(x, torch.Tensor) or x.dtype not in _NATIVE_DTYPES:
+        return False
+    if x.dim() < 1 or x.numel() == 0:
+        return False
+    if x.shape[-1] % last_mult or x.numel() % numel_mult:
+        return False
+    for t in same:
+        if t is not None and (t.dtype != x.dtype or t.shape != x.shape):
+            return False
+    for t in vecs:
+        if t is not None and not (t.is_floating_point()
+                                  and t.numel() == x.shape[-1]):
+            return False
+    return all(t is None or t.is_contiguous() for t in contiguous)
+
+
+def _norm_native_ok(x, w, b=None, residual=None):
+    """layer_norm / rms_norm / fused_rms_norm."""
+    return _kernel_ok(x, last_mult=8, same=(residual,), vecs=(w, b))
+
+
+def _bias_gelu_native_ok(x, bias=None):
+    return _kernel_ok(x, last_mult=8, vecs=(bias,))
+
+
+def _swiglu_native_ok(x):
+    """x: [..., 2*d] with d % 8 == 0."""
+    return _kernel_ok(x, last_mult=16)
+
+
+def _rope_native_ok(x, cos_t, sin_t, pos_offset=0):
+    """x: [B, S, H, Dh] with Dh/2 % 4 == 0; fp32 contiguous tables of
+    [>= S + pos_offset, Dh/2]."""
+    if not (_kernel_ok(x, last_mult=8, contiguous=(cos_t, sin_t))
+            and x.dim() == 4 and pos_offset >= 0):
+        return False
+    half = x.shape[-1] // 2
+    return all(t.dtype == torch.float32 and t.dim() == 2
+               and t.shape[1] == half and t.shape[0] >= x.shape[1] + pos_offset
+               for t in (cos_t, sin_t))
+
+
+def _dropout_add_native_ok(x, residual=None):
+    return _kernel_ok(x, numel_mult=8, same=(residual,))
+
+
+def _embedding_native_ok(table, ids):
+    return (_kernel_ok(table, last_mult=8) and table.dim() == 2
+            and not ids.is_floating_point() and ids.dtype != torch.bool)
+
+
+def _ce_native_ok(logits, labels):
+    return (_kernel_ok(logits) and not labels.is_floating_point()
+            and labels.dtype != torch.bool
+            and labels.numel() == logits.numel() // logits.shape[-1])
+
+
+def _reduce_native_ok(x):
+    """colsum / l2_norm_squared / amax_abs: any shape, scalar tails."""
+    return _kernel_ok(x)
+
+
+def _adamw_native_ok(master, param_out, grad, m, v):
+    if not all(t.dtype == torch.float32 and t.numel() == master.numel()
+               for t in (master, m, v)):
+        return False
+    if param_out is not None and not (param_out.dtype in _NATIVE_DTYPES
+                                      and param_out.numel() == master.numel()):
+        return False
+    return (_kernel_ok(grad) and grad.numel() == master.numel()
+            and all(t is None or t.is_contiguous()
+                    for t in (master, m, v, param_out)))
+
+
+def _as_dtype(t, dtype):
+    """Per-column parameter in the kernel's dtype (contiguous)."""
+    if t is None:
+        return None
+    return (t if t.dtype == dtype else t.to(dtype)).contiguous()
+
+
+# ---------------------------------------------------------------------------
 # layer_norm (paddle/phi/kernels/gpu/layer_norm_kernel.cu parity)
 # ---------------------------------------------------------------------------
 class _LayerNorm(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w, b, eps):
-        if _ext.use_native(x):
+        ctx.native = _ext.use_native(x) and _norm_native_ok(x, w, b)
+        ctx.w_dtype = w.dtype
+        ctx.b_dtype = b.dtype if b is not None else w.dtype
+        if ctx.native:
             C = _ext.get_ext()
-            y, mean, rstd = C.layer_norm_fwd(x.contiguous(), w.contiguous(),
-                                             b.contiguous() if b is not None else None, eps)
+            # saved for backward in the form the kernel reads
+            x, w = x.contiguous(), _as_dtype(w, x.dtype)
+            y, mean, rstd = C.layer_norm_fwd(x, w, _as_dtype(b, x.dtype), eps)
         else:
             xf = x.float()
             mean = xf.mean(-1).reshape(-1)
@@ -52,9 +159,11 @@ class _LayerNorm(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x, w, mean, rstd = ctx.saved_tensors
-        if _ext.use_native(x):
+        if ctx.native:
             C = _ext.get_ext()
-            dx, dw, db = C.layer_norm_bwd(dy.contiguous(), x, w, mean, rstd, ctx.has_bias)
+            dx, dw, db = C.layer_norm_bwd(dy.to(x.dtype).contiguous(), x, w,
+                                          mean, rstd, ctx.has_bias)
+            dw, db = dw.to(ctx.w_dtype), db.to(ctx.b_dtype)
         else:
             d = x.shape[-1]
             xf = x.float()
@@ -67,7 +176,7 @@ class _LayerNorm(torch.autograd.Function):
             s2 = g.mean(-1, keepdim=True)
             dx = (rs * (g - s2 - xhat * s1)).to(x.dtype)
             dw = (dyf * xhat).reshape(-1, d).sum(0).to(w.dtype)
-            db = dyf.reshape(-1, d).sum(0).to(w.dtype)
+            db = dyf.reshape(-1, d).sum(0).to(ctx.b_dtype)
         return dx, dw, (db if ctx.has_bias else None), None
 
 
@@ -85,9 +194,12 @@ def layer_norm(x, weight, bias=None, epsilon=1e-5):
 class _RMSNorm(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w, eps):
-        if _ext.use_native(x):
+        ctx.native = _ext.use_native(x) and _norm_native_ok(x, w)
+        ctx.w_dtype = w.dtype
+        if ctx.native:
             C = _ext.get_ext()
-            y, rstd = C.rms_norm_fwd(x.contiguous(), None, w.contiguous(), eps)
+            x, w = x.contiguous(), _as_dtype(w, x.dtype)
+            y, rstd = C.rms_norm_fwd(x, None, w, eps)
         else:
             xf = x.float()
             rstd = torch.rsqrt(xf.square().mean(-1) + eps).reshape(-1)
@@ -98,9 +210,10 @@ class _RMSNorm(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         x, w, rstd = ctx.saved_tensors
-        if _ext.use_native(x):
+        if ctx.native:
             C = _ext.get_ext()
-            dx, dw = C.rms_norm_bwd(dy.contiguous(), x, w, rstd)
+            dx, dw = C.rms_norm_bwd(dy.to(x.dtype).contiguous(), x, w, rstd)
+            dw = dw.to(ctx.w_dtype)
         else:
             d = x.shape[-1]
             xf, dyf = x.float(), dy.float()
@@ -127,9 +240,12 @@ class _FusedRMSNormResidual(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, residual, w, eps):
-        if _ext.use_native(x):
+        ctx.native = _ext.use_native(x) and _norm_native_ok(x, w, residual=residual)
+        ctx.w_dtype = w.dtype
+        if ctx.native:
             C = _ext.get_ext()
-            y, rstd, xr = C.rms_norm_fwd(x.contiguous(), residual.contiguous(), w.contiguous(), eps)
+            w = _as_dtype(w, x.dtype)
+            y, rstd, xr = C.rms_norm_fwd(x.contiguous(), residual.contiguous(), w, eps)
         else:
             xr = x + residual
             xf = xr.float()
@@ -141,9 +257,10 @@ class _FusedRMSNormResidual(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy, dxr):
         xr, w, rstd = ctx.saved_tensors
-        if _ext.use_native(xr):
+        if ctx.native:
             C = _ext.get_ext()
-            dx, dw = C.rms_norm_bwd(dy.contiguous(), xr, w, rstd)
+            dx, dw = C.rms_norm_bwd(dy.to(xr.dtype).contiguous(), xr, w, rstd)
+            dw = dw.to(ctx.w_dtype)
         else:
             d = xr.shape[-1]
             xf, dyf = xr.float(), dy.float()
@@ -177,15 +294,19 @@ class _SoftmaxCE(torch.autograd.Function):
         v = shp[-1]
         l2 = logits.reshape(-1, v)
         lab = labels.reshape(-1)
-        if _ext.use_native(logits):
+        ctx.native = _ext.use_native(logits) and _ce_native_ok(logits, labels)
+        if ctx.native:
             C = _ext.get_ext()
-            loss, lse = C.softmax_ce_fwd(l2.contiguous(), lab.contiguous(), ignore_index)
+            l2, lab = l2.contiguous(), lab.long().contiguous()
+            loss, lse = C.softmax_ce_fwd(l2, lab, ignore_index)
         else:
+            lab = lab.long()
             lf = l2.float()
             lse = torch.logsumexp(lf, -1)
-            safe = lab.clamp(min=0)
+            skip = (lab == ignore_index) | (lab < 0) | (lab >= v)
+            safe = lab.masked_fill(skip, 0)
             picked = lf.gather(1, safe.unsqueeze(1)).squeeze(1)
-            loss = torch.where(lab == ignore_index, torch.zeros_like(lse), lse - picked)
+            loss = torch.where(skip, torch.zeros_like(lse), lse - picked)
         ctx.save_for_backward(l2, lab, lse)
         ctx.ignore_index = ignore_index
         ctx.in_shape = shp
@@ -195,21 +316,33 @@ class _SoftmaxCE(torch.autograd.Function):
     def backward(ctx, dloss):
         l2, lab, lse = ctx.saved_tensors
         dl = dloss.reshape(-1).float().contiguous()
-        if _ext.use_native(l2):
+        if ctx.native:
             C = _ext.get_ext()
             dlogits = C.softmax_ce_bwd(dl, l2, lab, lse, ctx.ignore_index)
         else:
             p = torch.exp(l2.float() - lse.unsqueeze(1))
             onehot = torch.zeros_like(p)
-            safe = lab.clamp(min=0)
+            skip = (lab == ctx.ignore_index) | (lab < 0) | (lab >= l2.shape[-1])
+            safe = lab.masked_fill(skip, 0)
             onehot.scatter_(1, safe.unsqueeze(1), 1.0)
-            g = torch.where((lab == ctx.ignore_index).unsqueeze(1),
+            g = torch.where(skip.unsqueeze(1),
                             torch.zeros_like(dl).unsqueeze(1), dl.unsqueeze(1))
             dlogits = (g * (p - onehot)).to(l2.dtype)
         return dlogits.reshape(ctx.in_shape), None, None
 
 
 def softmax_cross_entropy(logits, labels, ignore_index=-100, reduction="none"):
+    """Per-row softmax cross entropy with hard labels.
+
+    A row whose label equals ignore_index, or lies outside [0, V), has
+    zero loss and zero gradient on the kernel and the torch path alike;
+    the kernel never reads logits at such a label.  -inf logits (banned
+    tokens) are handled as by torch: they carry probability 0.  A row
+    whose logits are all -inf is outside the contract.
+
+    reduction="mean" divides by the number of labels that differ from
+    ignore_index, as before: an out-of-range label adds 0 to the sum but
+    still counts in that denominator."""
     if _tracing():
         v = logits.shape[-1]
         loss = torch.nn.functional.cross_entropy(
@@ -233,9 +366,10 @@ class _BiasGelu(torch.autograd.Function):
     def forward(ctx, x, bias):
         ctx.save_for_backward(x, bias if bias is not None else torch.empty(0))
         ctx.has_bias = bias is not None
-        if _ext.use_native(x):
+        ctx.native = _ext.use_native(x) and _bias_gelu_native_ok(x, bias)
+        if ctx.native:
             C = _ext.get_ext()
-            return C.bias_gelu_fwd(x.contiguous(), bias.contiguous() if bias is not None else None)
+            return C.bias_gelu_fwd(x.contiguous(), _as_dtype(bias, x.dtype))
         v = x.float() + (bias.float() if bias is not None else 0.0)
         return torch.nn.functional.gelu(v).to(x.dtype)
 
@@ -244,16 +378,17 @@ class _BiasGelu(torch.autograd.Function):
         x, bias = ctx.saved_tensors
         b = bias if ctx.has_bias else None
         # d/dx gelu(x+b) == d/db gelu(x+b), so db = colsum(dx)
-        if _ext.use_native(x):
+        if ctx.native:
             C = _ext.get_ext()
-            dx = C.bias_gelu_bwd(dy.contiguous(), x, b.contiguous() if b is not None else None)
-            db = C.colsum(dx).to(dy.dtype) if ctx.has_bias else None
+            dx = C.bias_gelu_bwd(dy.to(x.dtype).contiguous(), x.contiguous(),
+                                 _as_dtype(b, x.dtype))
+            db = C.colsum(dx).to(b.dtype) if ctx.has_bias else None
         else:
             v = x.float() + (b.float() if b is not None else 0.0)
             cdf = 0.5 * (1.0 + torch.erf(v * 0.7071067811865476))
             pdf = 0.3989422804014327 * torch.exp(-0.5 * v * v)
             dx = (dy.float() * (cdf + v * pdf)).to(x.dtype)
-            db = dx.float().reshape(-1, dx.shape[-1]).sum(0).to(dy.dtype) if ctx.has_bias else None
+            db = dx.float().reshape(-1, dx.shape[-1]).sum(0).to(b.dtype) if ctx.has_bias else None
         return dx, db
 
 
@@ -270,10 +405,13 @@ def bias_gelu(x, bias=None):
 class _SwiGLU(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x):
+        ctx.native = _ext.use_native(x) and _swiglu_native_ok(x)
+        if ctx.native:
+            x = x.contiguous()
         ctx.save_for_backward(x)
-        if _ext.use_native(x):
+        if ctx.native:
             C = _ext.get_ext()
-            return C.swiglu_fwd(x.contiguous())
+            return C.swiglu_fwd(x)
         d = x.shape[-1] // 2
         g, u = x[..., :d].float(), x[..., d:].float()
         return (torch.nn.functional.silu(g) * u).to(x.dtype)
@@ -281,9 +419,9 @@ class _SwiGLU(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         (x,) = ctx.saved_tensors
-        if _ext.use_native(x):
+        if ctx.native:
             C = _ext.get_ext()
-            return C.swiglu_bwd(dy.contiguous(), x)
+            return C.swiglu_bwd(dy.to(x.dtype).contiguous(), x)
         d = x.shape[-1] // 2
         g, u = x[..., :d].float(), x[..., d:].float()
         sig = torch.sigmoid(g)
@@ -327,7 +465,8 @@ class _Rope(torch.autograd.Function):
     def forward(ctx, x, cos_t, sin_t, pos_offset):
         ctx.save_for_backward(cos_t, sin_t)
         ctx.pos_offset = pos_offset
-        if _ext.use_native(x):
+        ctx.native = _ext.use_native(x) and _rope_native_ok(x, cos_t, sin_t, pos_offset)
+        if ctx.native:
             C = _ext.get_ext()
             return C.rope_fwd(x.contiguous(), cos_t, sin_t, pos_offset, False)
         return _rope_ref(x, cos_t, sin_t, pos_offset, conj=False)
@@ -335,7 +474,7 @@ class _Rope(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         cos_t, sin_t = ctx.saved_tensors
-        if _ext.use_native(dy):
+        if ctx.native and _rope_native_ok(dy, cos_t, sin_t, ctx.pos_offset):
             C = _ext.get_ext()
             return C.rope_fwd(dy.contiguous(), cos_t, sin_t, ctx.pos_offset, True), None, None, None
         return _rope_ref(dy, cos_t, sin_t, ctx.pos_offset, conj=True), None, None, None
@@ -379,6 +518,12 @@ def fused_rotary_position_embedding(q, k=None, v=None, sin=None, cos=None,
     else:
         cos_t, sin_t = cos.float().reshape(-1, d)[..., : d // 2].contiguous(), \
                        sin.float().reshape(-1, d)[..., : d // 2].contiguous()
+    # checked here, before any kernel: a short table would be read past its end
+    if pos_offset < 0 or min(cos_t.shape[0], sin_t.shape[0]) < s + pos_offset:
+        raise ValueError(
+            f"fused_rotary_position_embedding: cos/sin hold "
+            f"{min(cos_t.shape[0], sin_t.shape[0])} positions, need seq_len + "
+            f"pos_offset = {s + pos_offset}")
     outs = [_Rope.apply(q, cos_t, sin_t, pos_offset)]
     if k is not None:
         outs.append(_Rope.apply(k, cos_t, sin_t, pos_offset))
@@ -682,7 +827,8 @@ class _DropoutAdd(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, residual, p, training):
         ctx.p = p if training else 0.0
-        if _ext.use_native(x):
+        ctx.native = _ext.use_native(x) and _dropout_add_native_ok(x, residual)
+        if ctx.native:
             C = _ext.get_ext()
             seed = int(torch.cuda.default_generators[x.device.index].initial_seed()) & 0x7FFFFFFF \
                 if x.is_cuda else 0
@@ -717,7 +863,7 @@ class _DropoutAdd(torch.autograd.Function):
         if p == 0:
             return dy, dres, None, None
         (mask,) = ctx.saved_tensors
-        if _ext.use_native(dy):
+        if ctx.native and _dropout_add_native_ok(dy):
             C = _ext.get_ext()
             dx = C.dropout_add_bwd(dy.contiguous(), mask, p)
         else:
@@ -741,16 +887,22 @@ class _Embedding(torch.autograd.Function):
         ctx.vocab = table.shape[0]
         ctx.padding_idx = padding_idx
         ctx.table_dtype = table.dtype
-        if _ext.use_native(table):
+        ctx.native = _ext.use_native(table) and _embedding_native_ok(table, ids)
+        if ctx.native:
             C = _ext.get_ext()
             return C.embedding_fwd(table.contiguous(), ids.contiguous().long(),
                                    padding_idx if padding_idx is not None else -1)
-        return torch.nn.functional.embedding(ids.long(), table, padding_idx=padding_idx)
+        out = torch.nn.functional.embedding(ids.long(), table)
+        if padding_idx is not None:
+            # paddle (and the kernel) return zeros for padded positions;
+            # torch's padding_idx only freezes that row's gradient
+            out = out.masked_fill((ids == padding_idx).unsqueeze(-1), 0)
+        return out
 
     @staticmethod
     def backward(ctx, dout):
         (ids,) = ctx.saved_tensors
-        if _ext.use_native(dout):
+        if ctx.native and _kernel_ok(dout, last_mult=8):
             C = _ext.get_ext()
             dtable = C.embedding_bwd(dout.contiguous(), ids.contiguous().long(), ctx.vocab,
                                      ctx.padding_idx if ctx.padding_idx is not None else -1)
@@ -784,7 +936,7 @@ def fused_adamw_step(master, param_out, grad, m, v, lr, beta1, beta2, eps,
     grad_scale folds grad-clip and the 1/world reduce divide into the
     kernel so no separate mul/cast pass touches HBM.
     adamw_ parity: paddle/phi/kernels/gpu/adamw_kernel.cu."""
-    if master.is_cuda and _ext.use_native(master):
+    if _ext.use_native(master) and _adamw_native_ok(master, param_out, grad, m, v):
         C = _ext.get_ext()
         C.adamw(master, param_out, grad.contiguous(), m, v, lr, beta1, beta2,
                 eps, weight_decay, beta1 ** step, beta2 ** step, grad_scale)
@@ -804,7 +956,7 @@ def fused_adamw_step(master, param_out, grad, m, v, lr, beta1, beta2, eps,
 
 
 def l2_norm_squared(x):
-    if x.is_cuda and _ext.use_native(x):
+    if _ext.use_native(x) and _reduce_native_ok(x):
         C = _ext.get_ext()
         return C.l2norm_sq(x.contiguous())
     return x.float().square().sum().reshape(1)
@@ -899,6 +1051,8 @@ def _wgrad(x2, dy2):
 
 
 def _colsum(dy2, dtype):
+    if not _reduce_native_ok(dy2):
+        return dy2.float().sum(0).to(dtype)
     C = _ext.get_ext()
     return C.colsum(dy2).to(dtype)
 
@@ -1014,7 +1168,7 @@ def fused_linear_param_grad_add(x, dy, dweight=None, dbias=None,
     if has_bias:
         if dbias is None:
             dbias = torch.zeros(dy2.shape[1], dtype=dy.dtype, device=dy.device)
-        if dy.is_cuda and _ext.use_native(dy):
+        if dy.is_cuda and _ext.use_native(dy) and _reduce_native_ok(dy2):
             C = _ext.get_ext()
             dbias.add_(C.colsum(dy2.contiguous()).to(dbias.dtype))
         else:
