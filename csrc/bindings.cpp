@@ -755,6 +755,87 @@ Tensor decode_gemm_int8(const Tensor& x, const Tensor& qw,
   return y;
 }
 
+// int4 weight-only storage shared by decode_gemm_int4 and dequant_int4:
+// qw int8 [K/2, N] contiguous (two codes per byte), scale fp32 [N]
+// (group_size -1) or [K/group_size, N] (group_size 64 | 128).  Returns K.
+static int64_t check_int4_weight(const Tensor& qw, const Tensor& scale,
+                                 int64_t group_size, const char* op) {
+  TORCH_CHECK(qw.is_cuda() && scale.is_cuda(), op, ": qw and scale must be GPU tensors");
+  TORCH_CHECK(qw.dim() == 2 && qw.is_contiguous(), op,
+              ": qw must be a contiguous [K/2, N] tensor");
+  TORCH_CHECK(qw.scalar_type() == torch::kChar, op, ": qw must be int8");
+  TORCH_CHECK(scale.scalar_type() == torch::kFloat && scale.is_contiguous(),
+              op, ": scale must be contiguous fp32");
+  TORCH_CHECK(group_size == -1 || group_size == 64 || group_size == 128, op,
+              ": group_size must be -1, 64 or 128, got ", group_size);
+  const int64_t k = qw.size(0) * 2, n = qw.size(1);
+  if (group_size == -1) {
+    TORCH_CHECK(scale.dim() == 1 && scale.size(0) == n, op,
+                ": per-channel scale must be [N]");
+  } else {
+    TORCH_CHECK(k % group_size == 0, op, ": K must be a multiple of group_size");
+    TORCH_CHECK(scale.dim() == 2 && scale.size(0) == k / group_size &&
+                scale.size(1) == n, op, ": group scale must be [K/group_size, N]");
+  }
+  return k;
+}
+
+Tensor decode_gemm_int4(const Tensor& x, const Tensor& qw, const Tensor& scale,
+                        const c10::optional<Tensor>& bias, int64_t group_size,
+                        int64_t ksplit) {
+  CHECK_IN(x);
+  TORCH_CHECK(x.dim() == 2 && x.scalar_type() == torch::kBFloat16,
+              "decode_gemm_int4: x must be a 2-D bf16 tensor");
+  const int64_t k = check_int4_weight(qw, scale, group_size, "decode_gemm_int4");
+  const int64_t m = x.size(0), n = qw.size(1);
+  TORCH_CHECK(x.size(1) == k, "decode_gemm_int4: qw.size(0)*2 must equal K");
+  TORCH_CHECK(m >= 1 && m <= 32, "decode_gemm_int4: 1 <= M <= 32, got ", m);
+  TORCH_CHECK(n > 0 && n % 256 == 0, "decode_gemm_int4: N % 256 == 0, got ", n);
+  TORCH_CHECK(k > 0 && k % 64 == 0 && k <= (int64_t(1) << 24),
+              "decode_gemm_int4: K % 64 == 0 (and K <= 2^24), got ", k);
+  TORCH_CHECK(ksplit >= 0, "decode_gemm_int4: ksplit >= 0");
+  const void* bp = nullptr;
+  if (bias.has_value()) {
+    TORCH_CHECK(bias->is_cuda() && bias->is_contiguous() &&
+                bias->scalar_type() == torch::kBFloat16 && bias->numel() == n,
+                "decode_gemm_int4: bias must be contiguous bf16 with N elements");
+    bp = bias->const_data_ptr();
+  }
+  if (ksplit == 0) {
+    // as the int8 streamer: ~1024 workgroups, but the fp32 partials cost
+    // ksplit*M*N*8 B of traffic next to a weight stream of only K*N/2 B,
+    // so every split keeps at least kmin k rows (4-8 LDS tiles)
+    const int64_t nblk = n / 256;
+    const int64_t kmin = nblk <= 24 ? 256 : 512;
+    ksplit = std::min<int64_t>(std::max<int64_t>(1, 1024 / nblk),
+                               std::max<int64_t>(1, k / kmin));
+  }
+  const int64_t ks = pa::decode_gemm_int4_splits(k, ksplit);
+  const int64_t mt = m <= 16 ? 16 : 32;
+  auto ws = torch::empty({ks, mt, n}, x.options().dtype(torch::kFloat));
+  auto y = torch::empty({m, n}, x.options());
+  pa::decode_gemm_int4(x.const_data_ptr(), qw.const_data_ptr(),
+                       scale.const_data_ptr<float>(), bp, y.mutable_data_ptr(),
+                       ws.mutable_data_ptr<float>(), m, n, k, group_size,
+                       ksplit, cur_stream());
+  return y;
+}
+
+Tensor dequant_int4(const Tensor& qw, const Tensor& scale, int64_t group_size,
+                    at::ScalarType out_dtype) {
+  const int64_t k = check_int4_weight(qw, scale, group_size, "dequant_int4");
+  const int64_t n = qw.size(1);
+  TORCH_CHECK(n % 8 == 0, "dequant_int4: N % 8 == 0, got ", n);
+  TORCH_CHECK(out_dtype == torch::kBFloat16 || out_dtype == torch::kFloat,
+              "dequant_int4: out_dtype must be bfloat16 or float32");
+  auto out = torch::empty({k, n}, qw.options().dtype(out_dtype));
+  pa::dequant_int4(qw.const_data_ptr(), scale.const_data_ptr<float>(),
+                   out.mutable_data_ptr(), k, n, group_size,
+                   out_dtype == torch::kBFloat16 ? pa::kBF16 : pa::kF32,
+                   cur_stream());
+  return out;
+}
+
 Tensor decode_gemm_mfma(const Tensor& x, const Tensor& w,
                         const c10::optional<Tensor>& bias) {
   CHECK_IN(x);
@@ -936,6 +1017,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("bias") = c10::nullopt);
   m.def("decode_gemm_int8", &decode_gemm_int8, py::arg("x"), py::arg("qw"),
         py::arg("scale"), py::arg("bias") = c10::nullopt);
+  m.def("decode_gemm_int4", &decode_gemm_int4, py::arg("x"), py::arg("qw"),
+        py::arg("scale"), py::arg("bias") = c10::nullopt,
+        py::arg("group_size") = -1, py::arg("ksplit") = 0);
+  m.def("dequant_int4", &dequant_int4, py::arg("qw"), py::arg("scale"),
+        py::arg("group_size"), py::arg("out_dtype"));
   m.def("moe_gate_topk", &moe_gate_topk);
   m.def("moe_assign_slots", &moe_assign_slots);
   m.def("gemm_fp8_nt", &gemm_fp8_nt, py::arg("a"), py::arg("bt"),

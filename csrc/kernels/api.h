@@ -238,6 +238,21 @@ void decode_gemm_mfma(const void* x, const void* w, const void* bias, void* y,
                  int64_t ldw, int64_t ksplit, hipStream_t s,
                  const float* chscale = nullptr, bool int8w = false);
 
+// weight-only int4 decode (decode_gemm_int4.hip).  qw int8 [K/2, N]: byte
+// (kp, n) = code[2kp, n] in the low nibble, code[2kp+1, n] in the high one,
+// codes -7..7; scale fp32 [N] (group_size -1) or [K/gs, N] (gs 64 | 128);
+// w ~ code * scale / 7.  M <= 32, N % 256 == 0, K % 64 == 0, K % gs == 0.
+// `workspace` holds [decode_gemm_int4_splits(k, ksplit), padded_m, N] fp32.
+int64_t decode_gemm_int4_splits(int64_t k, int64_t ksplit);
+void decode_gemm_int4(const void* x, const void* qw, const float* scale,
+                      const void* bias, void* y, float* workspace, int64_t m,
+                      int64_t n, int64_t k, int64_t group_size, int64_t ksplit,
+                      hipStream_t s);
+// packed [K/2, N] + scales -> bf16 | fp32 [K, N]; N % 8 == 0.  Each element
+// is float(code) * (scale * fp32(1/7)).
+void dequant_int4(const void* qw, const float* scale, void* out, int64_t k,
+                  int64_t n, int64_t group_size, int dtype, hipStream_t s);
+
 // ---- MoE routing (assign_pos/number_count/gate parity) --------------------
 void moe_gate_topk(const float* logits, float* topv, int* topi, float* me,
                    float* ce, int64_t t, int64_t e, int64_t k, hipStream_t s);

@@ -226,28 +226,154 @@ def _mk(cls_or_inst):
         return BaseQuanter()
 
 
-# -- weight-only int8 (serving decode path) ----------------------------------
+# -- weight-only int8 / int4 (serving decode path) ---------------------------
 # parity: paddle/phi/kernels/weight_quantize_kernel.cu + funcs/weight_only_gemv.cu
-def weight_quantize(w, algo="weight_only_int8"):
-    """w [K, N] (paddle Linear layout) -> (qweight [K, N] int8 row-major,
-    scale [N] fp32).  Per-output-channel absmax; w ~ qw * scale / 127.
+_WO_ALGOS = {"weight_only_int8": "int8", "weight_only_int4": "int4"}
+_WO_GROUP_SIZES = (-1, 64, 128)
 
-    The [K, N] layout feeds the MFMA W-streaming decode kernel with
-    coalesced rows (the round-1 [N, K] GEMV layout read 180-330 GB/s;
+
+def _wo_check(algo=None, weight_dtype=None, group_size=-1):
+    """Validate the weight-only arguments; returns "int8" | "int4"."""
+    if algo is not None:
+        if algo not in _WO_ALGOS:
+            raise ValueError(f"unknown weight-only algo {algo!r}; expected one "
+                             f"of {sorted(_WO_ALGOS)}")
+        weight_dtype = _WO_ALGOS[algo]
+    if weight_dtype not in ("int8", "int4"):
+        raise ValueError(f"weight_dtype must be 'int8' or 'int4', got "
+                         f"{weight_dtype!r}")
+    if group_size not in _WO_GROUP_SIZES:
+        raise ValueError(f"group_size must be one of {_WO_GROUP_SIZES}, got "
+                         f"{group_size!r}")
+    if weight_dtype == "int8" and group_size != -1:
+        raise NotImplementedError("int8 weight-only supports per-channel "
+                                  "scales only (group_size=-1)")
+    return weight_dtype
+
+
+def weight_quantize(w, algo="weight_only_int8", group_size=-1):
+    """w [K, N] (paddle Linear layout) -> (qweight, scale).
+
+    weight_only_int8: qweight [K, N] int8 row-major, scale [N] fp32,
+    per-output-channel absmax; w ~ qw * scale / 127.
+
+    weight_only_int4 storage format (K even; K % group_size == 0 with
+    groups):
+      * scale, fp32, absmax clamped at 1e-8: [N] over all of k for
+        group_size=-1, or [K/gs, N] with scale[g, n] taken over
+        k in [g*gs, (g+1)*gs) for group_size gs in (64, 128);
+      * codes q = round(w / scale * 7) clamped to [-7, 7] (never -8), so
+        w ~ q * scale / 7 -- the int8 convention with 7 for 127;
+      * qweight int8 [K/2, N] row-major: byte (kp, n) =
+        (q[2kp, n] & 0xF) | ((q[2kp+1, n] & 0xF) << 4), two's-complement
+        nibbles, even k in the low nibble.
+    Dequantization evaluates q * (scale * fp32(1/7)) in fp32.
+
+    The [K, N]-derived layouts feed the MFMA W-streaming decode kernels
+    with coalesced rows (the round-1 [N, K] GEMV layout read 180-330 GB/s;
     the streamer reads at the memory roofline on HALF the bytes)."""
     import torch
-    assert algo in ("weight_only_int8",)
+    wd = _wo_check(algo=algo, group_size=group_size)
     wf = w.detach().float()                          # [K, N]
-    scale = wf.abs().amax(dim=0).clamp(min=1e-8)     # [N]
-    q = torch.round(wf / scale.unsqueeze(0) * 127.0).clamp(-127, 127).to(torch.int8)
-    return q.contiguous(), scale
+    if wd == "int8":
+        scale = wf.abs().amax(dim=0).clamp(min=1e-8)     # [N]
+        q = torch.round(wf / scale.unsqueeze(0) * 127.0).clamp(-127, 127).to(torch.int8)
+        return q.contiguous(), scale
+    k, n = wf.shape
+    if k % 2:
+        raise ValueError(f"weight_only_int4 needs an even K, got {k}")
+    if group_size == -1:
+        scale = wf.abs().amax(dim=0).clamp(min=1e-8)     # [N]
+    else:
+        if k % group_size:
+            raise ValueError(f"K={k} is not a multiple of group_size={group_size}")
+        scale = wf.reshape(k // group_size, group_size, n).abs().amax(dim=1)
+        scale = scale.clamp(min=1e-8)                    # [K/gs, N]
+    q = torch.round(wf / _wo_int4_expand_scale(scale, k, group_size) * 7.0)
+    q = q.clamp(-7, 7).to(torch.int32)
+    packed = (q[0::2] & 0xF) | ((q[1::2] & 0xF) << 4)    # 0..255
+    return packed.to(torch.uint8).view(torch.int8).contiguous(), scale.contiguous()
 
 
-def weight_only_linear(x, qweight, scale, bias=None, weight_dtype="int8"):
+def _wo_int4_expand_scale(scale, k, group_size):
+    """scale [N] | [K/gs, N] -> broadcastable against [K, N]."""
+    if group_size == -1:
+        return scale.reshape(1, -1)
+    return scale.repeat_interleave(group_size, dim=0)
+
+
+def _wo_int4_unpack(qweight):
+    """packed int8 [K/2, N] -> codes int8 [K, N] (even k = low nibble)."""
+    import torch
+    lo = (((qweight & 0xF) ^ 8) - 8).to(torch.int8)   # sign-extend 4 bits
+    hi = qweight >> 4                                 # arithmetic shift
+    return torch.stack((lo, hi), dim=1).reshape(2 * qweight.shape[0],
+                                                qweight.shape[1])
+
+
+def _wo_int4_scale_ok(qweight, scale, group_size):
+    """scale has the documented shape for qweight / group_size."""
+    if qweight.dim() != 2 or group_size not in _WO_GROUP_SIZES:
+        return False
+    k, n = 2 * qweight.shape[0], qweight.shape[1]
+    if group_size == -1:
+        return tuple(scale.shape) == (n,)
+    return k % group_size == 0 and tuple(scale.shape) == (k // group_size, n)
+
+
+def _wo_int4_dequant_torch(qweight, scale, group_size):
+    """torch composite of the documented format: fp32 [K, N]."""
+    if not _wo_int4_scale_ok(qweight, scale, group_size):
+        raise ValueError(
+            f"int4 scale shape {tuple(scale.shape)} does not fit qweight "
+            f"{tuple(qweight.shape)} with group_size={group_size}")
+    k = 2 * qweight.shape[0]
+    s = _wo_int4_expand_scale(scale.float(), k, group_size)
+    return _wo_int4_unpack(qweight).float() * (s * (1.0 / 7.0))
+
+
+def _wo_int4_dequant_native_ok(qweight, scale, group_size, out_dtype):
+    """Contract of the dequant_int4 kernel (pure: dtypes, shapes,
+    contiguity)."""
+    import torch
+    return (isinstance(qweight, torch.Tensor) and isinstance(scale, torch.Tensor)
+            and qweight.dtype == torch.int8 and qweight.dim() == 2
+            and qweight.is_contiguous() and qweight.numel() > 0
+            and qweight.shape[1] % 8 == 0
+            and scale.dtype == torch.float32 and scale.is_contiguous()
+            and _wo_int4_scale_ok(qweight, scale, group_size)
+            and out_dtype in (torch.bfloat16, torch.float32))
+
+
+def _wo_int4_native_ok(x, qweight, scale, bias=None, group_size=-1):
+    """Contract of the decode_gemm_int4 streamer (pure: dtypes, shapes,
+    contiguity -- no CUDA call): bf16 x with <= 32 rows, N % 256 == 0,
+    K % 64 == 0, group_size in (-1, 64, 128) with K % group_size == 0."""
+    import torch
+    if not (isinstance(x, torch.Tensor) and x.dtype == torch.bfloat16
+            and x.dim() >= 1 and x.numel() > 0):
+        return False
+    if not _wo_int4_dequant_native_ok(qweight, scale, group_size, x.dtype):
+        return False
+    k, n = 2 * qweight.shape[0], qweight.shape[1]
+    if x.shape[-1] != k or x.numel() // k > 32:
+        return False
+    if n % 256 or k % 64:
+        return False
+    return bias is None or (bias.is_floating_point() and bias.numel() == n)
+
+
+def weight_only_linear(x, qweight, scale, bias=None, weight_dtype="int8",
+                       group_size=-1):
     """x [..., K] @ dequant(qweight) + bias.  Decode shapes (<= 32 rows)
-    run the int8 MFMA W-streaming kernel; fallback dequantizes."""
+    run the int8 / int4 MFMA W-streaming kernel; int4 prefill shapes
+    dequantize in one dequant_int4 pass; the fallback dequantizes in
+    torch.  int4 operands use the weight_quantize storage format."""
     import torch
     from .. import _ext
+    wd = _wo_check(weight_dtype=weight_dtype, group_size=group_size)
+    if wd == "int4":
+        return _wo_int4_linear(x, qweight, scale, bias, group_size)
     k, n = qweight.shape
     if x.is_cuda and _ext.use_native(x):
         rows = x.numel() // x.shape[-1]
@@ -264,38 +390,71 @@ def weight_only_linear(x, qweight, scale, bias=None, weight_dtype="int8"):
     return out
 
 
+def _wo_int4_linear(x, qweight, scale, bias, group_size):
+    from .. import _ext
+    n = qweight.shape[1]
+    w = None
+    if x.is_cuda and _ext.use_native(x):
+        C = _ext.get_ext()
+        if _wo_int4_native_ok(x, qweight, scale, bias, group_size):
+            b = bias.to(x.dtype).contiguous() if bias is not None else None
+            out = C.decode_gemm_int4(x.reshape(-1, x.shape[-1]).contiguous(),
+                                     qweight, scale, b, group_size, 0)
+            return out.reshape(*x.shape[:-1], n)
+        if _wo_int4_dequant_native_ok(qweight, scale, group_size, x.dtype):
+            w = C.dequant_int4(qweight, scale, group_size, x.dtype)
+    if w is None:
+        w = _wo_int4_dequant_torch(qweight, scale, group_size).to(x.dtype)
+    out = x @ w
+    if bias is not None:
+        out = out + bias
+    return out
+
+
 class WeightOnlyLinear(__import__("torch").nn.Module):
     """Drop-in replacement for a (paddle-layout) nn.Linear holding int8
-    weights; decode shapes run the MFMA W-streaming int8 kernel, larger
-    shapes dequantize on the fly.  Reference: paddle/nn/quant
-    weight-only path."""
+    or packed int4 weights; decode shapes run the MFMA W-streaming
+    kernels, larger shapes dequantize on the fly.  Reference:
+    paddle/nn/quant weight-only path."""
 
-    def __init__(self, qweight, scale, bias=None):
+    def __init__(self, qweight, scale, bias=None, weight_dtype="int8",
+                 group_size=-1):
         super().__init__()
+        self.weight_dtype = _wo_check(weight_dtype=weight_dtype,
+                                      group_size=group_size)
+        self.group_size = group_size
         self.register_buffer("qweight", qweight)
         self.register_buffer("scale", scale)
         self.register_buffer("wo_bias", bias)
-        self.in_features = qweight.shape[0]
+        # int4 packs two k rows per byte
+        self.in_features = qweight.shape[0] * (2 if self.weight_dtype == "int4" else 1)
         self.out_features = qweight.shape[1]
 
     @classmethod
-    def from_linear(cls, linear):
-        qw, sc = weight_quantize(linear.weight.detach())
+    def from_linear(cls, linear, algo="weight_only_int8", group_size=-1):
+        qw, sc = weight_quantize(linear.weight.detach(), algo=algo,
+                                 group_size=group_size)
         dev = linear.weight.device
         bias = getattr(linear, "bias", None)
         return cls(qw.to(dev), sc.to(dev),
-                   bias.detach().clone() if bias is not None else None)
+                   bias.detach().clone() if bias is not None else None,
+                   weight_dtype=_WO_ALGOS[algo], group_size=group_size)
 
     def forward(self, x):
-        return weight_only_linear(x, self.qweight, self.scale, self.wo_bias)
+        return weight_only_linear(x, self.qweight, self.scale, self.wo_bias,
+                                  weight_dtype=self.weight_dtype,
+                                  group_size=self.group_size)
 
 
-def quantize_linears_(model, min_features=1024, skip=("lm_head",)):
+def quantize_linears_(model, min_features=1024, skip=("lm_head",),
+                      algo="weight_only_int8", group_size=-1):
     """Replace every Linear child of `model` (recursively) whose weight
     is at least [min_features, min_features] with a WeightOnlyLinear --
-    int8 weights, ~2x less weight memory for serving.  Returns the
+    int8 weights (~2x less weight memory for serving) or, with
+    algo="weight_only_int4", packed int4 weights (~4x less).  Returns the
     number of layers converted."""
     import torch
+    _wo_check(algo=algo, group_size=group_size)
     n = 0
 
     def walk(mod, prefix=""):
@@ -309,7 +468,8 @@ def quantize_linears_(model, min_features=1024, skip=("lm_head",)):
             w = getattr(child, "weight", None)
             if (type(child).__name__ == "Linear" and isinstance(w, torch.Tensor)
                     and w.dim() == 2 and min(w.shape) >= min_features):
-                mod._modules[name] = WeightOnlyLinear.from_linear(child)
+                mod._modules[name] = WeightOnlyLinear.from_linear(
+                    child, algo=algo, group_size=group_size)
                 n += 1
             else:
                 walk(child, full + ".")

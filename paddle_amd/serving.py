@@ -237,16 +237,23 @@ class GPTModelRunner:
 
     def __init__(self, model, num_blocks=1024, block_size=16,
                  device=None, dtype=None, max_seq=2048, use_graphs=True,
-                 weight_only=False):
+                 weight_only=False, weight_only_group_size=-1):
         import math
         from .ops import functional as hot
         self.hot = hot
         self.model = model.eval()
         if weight_only:
-            # int8 weight-only decode: ~2x less weight memory; decode
-            # linears run the MFMA W-streaming int8 kernel
+            # weight-only decode: True | "int8" (~2x less weight memory) or
+            # "int4" (~4x less, weight_only_group_size -1 | 64 | 128);
+            # decode linears run the MFMA W-streaming int8 / int4 kernel
+            if weight_only is not True and weight_only not in ("int8", "int4"):
+                raise ValueError("weight_only must be False, True, 'int8' or "
+                                 f"'int4', got {weight_only!r}")
+            wdt = "int8" if weight_only is True else weight_only
             from .quantization import quantize_linears_
-            quantize_linears_(self.model, skip=("lm_head", "embeddings"))
+            quantize_linears_(self.model, skip=("lm_head", "embeddings"),
+                              algo=f"weight_only_{wdt}",
+                              group_size=weight_only_group_size)
         cfg = model.cfg
         self.H = cfg.num_heads
         self.HKV = getattr(cfg, "num_kv_heads", cfg.num_heads)   # GQA-aware
@@ -492,10 +499,15 @@ class LlamaModelRunner(GPTModelRunner):
         for layer in model.llama.layers:
             a = layer.self_attn
             projs = (a.q_proj, a.k_proj, a.v_proj)
-            if all(hasattr(p, "qweight") for p in projs):   # weight-only int8
+            if all(hasattr(p, "qweight") for p in projs):   # weight-only
+                # entry: (weight dtype, qweight, scale, group size).  int8
+                # [K, N] and packed int4 [K/2, N] both concatenate along n;
+                # per-channel scales are [N], group scales [K/gs, N]
+                wdt, gs = a.q_proj.weight_dtype, a.q_proj.group_size
                 qw = torch.cat([p.qweight for p in projs], dim=1).contiguous()
-                sc = torch.cat([p.scale for p in projs]).contiguous()
-                self._qkv_fused.append(("int8", qw, sc))
+                sc = torch.cat([p.scale for p in projs],
+                               dim=a.q_proj.scale.dim() - 1).contiguous()
+                self._qkv_fused.append((wdt, qw, sc, gs))
             elif all(getattr(p, "weight", None) is not None for p in projs):
                 w = torch.cat([p.weight for p in projs], dim=1).contiguous()
                 qo = a.q_proj.weight.shape[1]
@@ -503,11 +515,11 @@ class LlamaModelRunner(GPTModelRunner):
                 a.q_proj.weight.data = w[:, :qo]
                 a.k_proj.weight.data = w[:, qo:qo + ko]
                 a.v_proj.weight.data = w[:, qo + ko:]
-                self._qkv_fused.append(("bf16", w, None))
+                self._qkv_fused.append(("bf16", w, None, -1))
             else:
                 # mixed (e.g. GQA k/v under quantize_linears_' min_features
                 # cutoff while q was converted): run the module calls
-                self._qkv_fused.append(("none", None, None))
+                self._qkv_fused.append(("none", None, None, -1))
 
     def _rope_rows(self, x, pos):
         """x [B, 1, H, D] at per-row absolute positions pos [B] (long)."""
@@ -562,12 +574,13 @@ class LlamaModelRunner(GPTModelRunner):
         ko = self.HKV * self.D
         for li, layer in enumerate(m.llama.layers):
             h = layer.input_layernorm(x)
-            kind, w, sc = self._qkv_fused[li]
+            kind, w, sc, gs = self._qkv_fused[li]
             h2 = h.reshape(B, -1)
             at = layer.self_attn
-            if kind == "int8":
+            if kind in ("int8", "int4"):
                 from .quantization import weight_only_linear
-                qkv = weight_only_linear(h2, w, sc)
+                qkv = weight_only_linear(h2, w, sc, weight_dtype=kind,
+                                         group_size=gs)
             elif kind == "bf16":
                 qkv = torch.matmul(h2, w)
             else:

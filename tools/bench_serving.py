@@ -18,13 +18,14 @@ from paddle_amd.serving import Engine, GPTModelRunner, Request  # noqa: E402
 
 
 def run_one(tag, model, n_req=64, prompt_len=128, gen_len=128, max_batch=32,
-            num_blocks=4096, weight_only=False, runner_cls="gpt"):
+            num_blocks=4096, weight_only=False, runner_cls="gpt",
+            group_size=-1):
     cls = GPTModelRunner
     if runner_cls == "llama":
         from paddle_amd.serving import LlamaModelRunner
         cls = LlamaModelRunner
     runner = cls(model, num_blocks=num_blocks, block_size=16,
-                 weight_only=weight_only)
+                 weight_only=weight_only, weight_only_group_size=group_size)
     runner.precapture((max_batch,))    # decode graph capture out of ttft
     eng = Engine(runner, num_blocks=num_blocks, block_size=16,
                  max_batch=max_batch)
@@ -65,25 +66,33 @@ def main():
     ap.add_argument("--model", default="gpt-350m",
                     choices=["gpt-350m", "gpt3-6.7b", "llama2-7b"])
     ap.add_argument("--weight-only", action="store_true",
-                    help="int8 weight-only decode (MFMA W-streamer)")
+                    help="weight-only decode (MFMA W-streamer); int8 unless "
+                         "--weight-only-dtype says otherwise")
+    ap.add_argument("--weight-only-dtype", choices=["int8", "int4"],
+                    default=None, help="implies --weight-only")
+    ap.add_argument("--group-size", type=int, default=-1,
+                    choices=[-1, 64, 128], help="int4 scale group size")
     args = ap.parse_args()
     paddle.seed(0)
-    tag_sfx = " int8-wo" if args.weight_only else ""
+    wo = args.weight_only_dtype or ("int8" if args.weight_only else False)
+    tag_sfx = ""
+    if wo:
+        tag_sfx = f" {wo}-wo" + (f"-gs{args.group_size}" if args.group_size > 0 else "")
+    kw = dict(weight_only=wo, group_size=args.group_size)
     if args.model == "gpt-350m":
         cfg = GPTConfig(vocab_size=50304, hidden_size=1024, num_layers=24,
                         num_heads=16, intermediate_size=4096, max_seq_len=2048)
         m = GPTForPretraining(cfg).to("cuda", torch.bfloat16)
-        run_one("gpt-350M" + tag_sfx, m, weight_only=args.weight_only)
+        run_one("gpt-350M" + tag_sfx, m, **kw)
     elif args.model == "gpt3-6.7b":
         m = build_gpt("gpt3-6.7b", max_seq_len=2048).to("cuda", torch.bfloat16)
         run_one("gpt3-6.7B" + tag_sfx, m, n_req=64, max_batch=32,
-                num_blocks=8192, weight_only=args.weight_only)
+                num_blocks=8192, **kw)
     else:
         from paddle_amd.models.llama import build_llama
         m = build_llama("llama2-7b", max_seq_len=2048).to("cuda", torch.bfloat16)
         run_one("llama2-7B" + tag_sfx, m, n_req=64, max_batch=32,
-                num_blocks=8192, weight_only=args.weight_only,
-                runner_cls="llama")
+                num_blocks=8192, runner_cls="llama", **kw)
 
 
 if __name__ == "__main__":
