@@ -95,14 +95,76 @@ std::vector<Tensor> layer_norm_fwd(const Tensor& x, const Tensor& w,
   return {y, mean, rstd};
 }
 
+// h = x + residual, y = LN(h).  d > kLnFusedMaxD runs the two kernels the
+// fused one replaces, on the same contract.
+std::vector<Tensor> add_layer_norm_fwd(const Tensor& x, const Tensor& residual,
+                                       const Tensor& w,
+                                       const c10::optional<Tensor>& b, double eps) {
+  CHECK_IN(x);
+  check_rows(x, "add_layer_norm");
+  int64_t d = x.size(-1), n = x.numel() / d;
+  CHECK_SAME(residual, x);
+  TORCH_CHECK(residual.sizes() == x.sizes(), "residual must have the shape of x");
+  CHECK_VEC(w, x, d);
+  if (b.has_value()) CHECK_VEC((*b), x, d);
+  auto h = torch::empty_like(x);
+  auto y = torch::empty_like(x);
+  auto mean = torch::empty({n}, x.options().dtype(torch::kFloat));
+  auto rstd = torch::empty({n}, x.options().dtype(torch::kFloat));
+  const void* bp = b.has_value() ? b->const_data_ptr() : nullptr;
+  if (pa::ln_fused_ok(d)) {
+    pa::add_layer_norm_fwd(x.const_data_ptr(), residual.const_data_ptr(),
+                           w.const_data_ptr(), bp, h.mutable_data_ptr(),
+                           y.mutable_data_ptr(), mean.mutable_data_ptr<float>(),
+                           rstd.mutable_data_ptr<float>(), n, d, (float)eps,
+                           dt_of(x), cur_stream());
+  } else {
+    pa::dropout_add_fwd(x.const_data_ptr(), residual.const_data_ptr(),
+                        h.mutable_data_ptr(), nullptr, x.numel(), 0.f, 0, 0,
+                        dt_of(x), cur_stream());
+    pa::layer_norm_fwd(h.const_data_ptr(), w.const_data_ptr(), bp,
+                       y.mutable_data_ptr(), mean.mutable_data_ptr<float>(),
+                       rstd.mutable_data_ptr<float>(), n, d, (float)eps, dt_of(x),
+                       cur_stream());
+  }
+  return {h, y, mean, rstd};
+}
+
+int64_t ln_bwd_grid_cap() { return pa::kLnBwdGridCap; }
+bool ln_fused_ok(int64_t d) { return pa::ln_fused_ok(d); }
+
+// dres (optional): residual-stream gradient added to dx in the kernel.
+// fused = false, or d > kLnFusedMaxD: the two-kernel path (dx, then dw/db
+// from a second read), with dres added by a tensor add.  grid_cap: row-block
+// cap of the one-pass kernel, 0 = the measured default.
 std::vector<Tensor> layer_norm_bwd(const Tensor& dy, const Tensor& x,
                                    const Tensor& w, const Tensor& mean,
-                                   const Tensor& rstd, bool has_bias) {
+                                   const Tensor& rstd, bool has_bias,
+                                   const c10::optional<Tensor>& dres,
+                                   bool fused, int64_t grid_cap) {
   CHECK_IN(x);
   check_rows(x, "layer_norm_bwd");
   int64_t d = x.size(-1), n = x.numel() / d;
   CHECK_SAME(dy, x); CHECK_VEC(w, x, d);
   CHECK_STAT(mean, n); CHECK_STAT(rstd, n);
+  if (dres.has_value()) CHECK_SAME((*dres), x);
+  TORCH_CHECK(grid_cap >= 0 && grid_cap <= 65536, "layer_norm_bwd: bad grid_cap");
+  if (fused && pa::ln_fused_ok(d)) {
+    auto dx = torch::empty_like(x);
+    auto dw = torch::empty({d}, x.options().dtype(torch::kFloat));
+    auto db = torch::empty({d}, x.options().dtype(torch::kFloat));
+    int grid = pa::ln_bwd_fused_grid(n, (int)grid_cap);
+    auto ws = torch::empty({(int64_t)grid * 2 * d}, x.options().dtype(torch::kFloat));
+    pa::layer_norm_bwd_fused(dy.const_data_ptr(), x.const_data_ptr(),
+                             w.const_data_ptr(), mean.const_data_ptr<float>(),
+                             rstd.const_data_ptr<float>(),
+                             dres.has_value() ? dres->const_data_ptr() : nullptr,
+                             dx.mutable_data_ptr(), dw.mutable_data_ptr<float>(),
+                             db.mutable_data_ptr<float>(),
+                             ws.mutable_data_ptr<float>(), grid, n, d, dt_of(x),
+                             cur_stream());
+    return {dx, dw, db};
+  }
   auto dx = torch::empty_like(x);
   auto dw = torch::zeros({d}, x.options().dtype(torch::kFloat));
   auto db = torch::zeros({d}, x.options().dtype(torch::kFloat));
@@ -115,6 +177,7 @@ std::vector<Tensor> layer_norm_bwd(const Tensor& dy, const Tensor& x,
                           mean.const_data_ptr<float>(), rstd.const_data_ptr<float>(),
                           dw.mutable_data_ptr<float>(), db.mutable_data_ptr<float>(),
                           n, d, dt_of(x), cur_stream(), ws.mutable_data_ptr<float>());
+  if (dres.has_value()) dx.add_(dres->view_as(dx));
   // dw/db stay fp32: the caller casts them to the parameter's dtype, which
   // under amp O2 is fp32 next to bf16 activations
   return {dx, dw, db};
@@ -218,6 +281,41 @@ Tensor bias_gelu_bwd(const Tensor& dy, const Tensor& x, const c10::optional<Tens
                     bias.has_value() ? bias->const_data_ptr() : nullptr,
                     dx.mutable_data_ptr(), n, d, dt_of(x), cur_stream());
   return dx;
+}
+
+// {dx, db}: db fp32 [d] = column sum of dx as stored.  One kernel plus a
+// partials reduce when a grid keeps each thread on its columns (fused =
+// true and bias_gelu_bwd_db_grid > 0), else bias_gelu_bwd then colsum.
+std::vector<Tensor> bias_gelu_bwd_db(const Tensor& dy, const Tensor& x,
+                                     const c10::optional<Tensor>& bias, bool fused) {
+  CHECK_IN(x);
+  check_rows(x, "bias_gelu_bwd_db");
+  int64_t d = x.size(-1), n = x.numel() / d;
+  CHECK_SAME(dy, x);
+  if (bias.has_value()) CHECK_VEC((*bias), x, d);
+  const void* bp = bias.has_value() ? bias->const_data_ptr() : nullptr;
+  auto dx = torch::empty_like(x);
+  int grid = fused ? pa::bias_gelu_bwd_db_grid(n, d) : 0;
+  if (grid > 0) {
+    const int64_t w = d % 16 == 0 ? 16 : 8;
+    auto db = torch::empty({d}, x.options().dtype(torch::kFloat));
+    auto ws = torch::empty({(int64_t)grid * 256 * w}, x.options().dtype(torch::kFloat));
+    pa::bias_gelu_bwd_db(dy.const_data_ptr(), x.const_data_ptr(), bp,
+                         dx.mutable_data_ptr(), db.mutable_data_ptr<float>(),
+                         ws.mutable_data_ptr<float>(), grid, n, d, dt_of(x),
+                         cur_stream());
+    return {dx, db};
+  }
+  pa::bias_gelu_bwd(dy.const_data_ptr(), x.const_data_ptr(), bp,
+                    dx.mutable_data_ptr(), n, d, dt_of(x), cur_stream());
+  auto db = torch::zeros({d}, x.options().dtype(torch::kFloat));
+  pa::colsum(dx.const_data_ptr(), db.mutable_data_ptr<float>(), n, d, dt_of(x),
+             cur_stream());
+  return {dx, db};
+}
+
+bool bias_gelu_bwd_db_fused(int64_t n, int64_t d) {
+  return pa::bias_gelu_bwd_db_grid(n, d) > 0;
 }
 
 Tensor swiglu_fwd(const Tensor& x) {
@@ -423,6 +521,31 @@ std::vector<Tensor> flash_attn_bwd(const Tensor& dout, const Tensor& q, const Te
                      mp, ms, (float)pdrop, (uint64_t)seed, (uint64_t)offset,
                      cur_stream());
   return {dq, dk, dv};
+}
+
+// delta[b, h, sq] = rowsum(dout * o): the first kernel of flash_attn_bwd on
+// its own.  dout / o: bf16 [b, h, sq, d] views with head_dim contiguous.
+Tensor flash_attn_bwd_delta(const Tensor& dout, const Tensor& o) {
+  TORCH_CHECK(dout.is_cuda() && o.is_cuda() &&
+              dout.scalar_type() == torch::kBFloat16 &&
+              o.scalar_type() == torch::kBFloat16 && dout.dim() == 4 &&
+              dout.sizes() == o.sizes() && dout.numel() > 0,
+              "flash_attn_bwd_delta: dout / o must be bf16 [b, h, sq, d] GPU tensors of one shape");
+  int64_t b = o.size(0), h = o.size(1), sq = o.size(2), d = o.size(3);
+  TORCH_CHECK(d == 128 || d == 64, "flash_attn_bwd_delta: head_dim must be 64 or 128");
+  int64_t dos[3], os[3];
+  fa_strides(dout, dos); fa_strides(o, os);
+  for (int i = 0; i < 3; ++i)
+    TORCH_CHECK(dos[i] % 8 == 0 && os[i] % 8 == 0 && dos[i] >= 0 && os[i] >= 0,
+                "flash_attn_bwd_delta: strides must keep rows 16-byte aligned");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(dout.const_data_ptr()) % 16 == 0 &&
+              reinterpret_cast<uintptr_t>(o.const_data_ptr()) % 16 == 0,
+              "flash_attn_bwd_delta: 16-byte aligned data required");
+  auto delta = torch::empty({b, h, sq}, o.options().dtype(torch::kFloat));
+  pa::flash_attn_bwd_delta(dout.const_data_ptr(), o.const_data_ptr(),
+                           delta.mutable_data_ptr<float>(), b, h, sq, d, dos, os,
+                           cur_stream());
+  return delta;
 }
 
 // host-side block map for the varlen kernels: (seq, offset) per block
@@ -988,7 +1111,19 @@ Tensor mfma_probe32(const Tensor& a, const Tensor& bt) {
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("layer_norm_fwd", &layer_norm_fwd);
-  m.def("layer_norm_bwd", &layer_norm_bwd);
+  m.def("layer_norm_bwd", &layer_norm_bwd, py::arg("dy"), py::arg("x"),
+        py::arg("w"), py::arg("mean"), py::arg("rstd"), py::arg("has_bias"),
+        py::arg("dres") = c10::nullopt, py::arg("fused") = true,
+        py::arg("grid_cap") = 0);
+  m.def("add_layer_norm_fwd", &add_layer_norm_fwd, py::arg("x"),
+        py::arg("residual"), py::arg("w"), py::arg("b") = c10::nullopt,
+        py::arg("eps") = 1e-5);
+  m.def("ln_bwd_grid_cap", &ln_bwd_grid_cap);
+  m.def("ln_fused_ok", &ln_fused_ok);
+  m.def("bias_gelu_bwd_db", &bias_gelu_bwd_db, py::arg("dy"), py::arg("x"),
+        py::arg("bias") = c10::nullopt, py::arg("fused") = true);
+  m.def("bias_gelu_bwd_db_fused", &bias_gelu_bwd_db_fused);
+  m.def("flash_attn_bwd_delta", &flash_attn_bwd_delta);
   m.def("rms_norm_fwd", &rms_norm_fwd);
   m.def("rms_norm_bwd", &rms_norm_bwd);
   m.def("softmax_ce_fwd", &softmax_ce_fwd);

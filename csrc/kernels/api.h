@@ -23,6 +23,29 @@ void layer_norm_bwd_dwdb(const void* dy, const void* x, const float* mean,
                          int64_t d, int dtype, hipStream_t s,
                          float* ws = nullptr);
 
+// Register-resident fused norms (d % 8 == 0, d <= kLnFusedMaxD).
+constexpr int64_t kLnFusedMaxD = 8192;
+// row-block cap of the one-pass backward (measured, docs/KERNELS.md)
+constexpr int kLnBwdGridCap = 1024;
+bool ln_fused_ok(int64_t d);
+int ln_bwd_fused_grid(int64_t n, int cap);  // cap <= 0: kLnBwdGridCap
+// h = x + residual (stored), y = LN(h); bit-equal to dropout_add_fwd(p=0)
+// followed by layer_norm_fwd
+void add_layer_norm_fwd(const void* x, const void* residual, const void* w,
+                        const void* b, void* h, void* y, float* mean,
+                        float* rstd, int64_t n, int64_t d, float eps, int dtype,
+                        hipStream_t s);
+// dx (+ dres, may be null), dw and db (may be null) from one read of dy and
+// x.  ws: fp32 [grid, 2, d] partials, grid = ln_bwd_fused_grid(n, cap).
+void layer_norm_bwd_fused(const void* dy, const void* x, const void* w,
+                          const float* mean, const float* rstd,
+                          const void* dres, void* dx, float* dw, float* db,
+                          float* ws, int grid, int64_t n, int64_t d, int dtype,
+                          hipStream_t s);
+// out0[d] (and out1[d], may be null) = sum over parts of ws[parts][nout][d]
+void ws_reduce(const float* ws, float* out0, float* out1, int parts, int nout,
+               int64_t d, hipStream_t s);
+
 void rms_norm_fwd(const void* x, const void* residual, const void* w, void* y,
                   void* res_out, float* rstd, int64_t n, int64_t d, float eps,
                   int dtype, hipStream_t s);
@@ -51,6 +74,14 @@ void bias_gelu_fwd(const void* x, const void* bias, void* y, int64_t n,
 // dx = gelu'(x+bias) * dy  (dbias reduced by caller or dwdb-style kernel)
 void bias_gelu_bwd(const void* dy, const void* x, const void* bias, void* dx,
                    int64_t n, int64_t d, int dtype, hipStream_t s);
+// Same dx, plus db[d] = colsum(dx as stored) from per-thread partials.
+// grid = bias_gelu_bwd_db_grid(n, d); 0 means no grid keeps a thread on the
+// same columns and the caller runs bias_gelu_bwd + colsum.  ws: fp32
+// [grid * 256 * W] with W = 16 if d % 16 == 0 else 8.
+int bias_gelu_bwd_db_grid(int64_t n, int64_t d);
+void bias_gelu_bwd_db(const void* dy, const void* x, const void* bias, void* dx,
+                      float* db, float* ws, int grid, int64_t n, int64_t d,
+                      int dtype, hipStream_t s);
 
 // swiglu: x [n, 2d] = [gate | up]; y [n, d] = silu(gate) * up
 void swiglu_fwd(const void* x, void* y, int64_t n, int64_t d, int dtype,
@@ -124,6 +155,10 @@ void flash_attn_bwd(const void* dout, const void* q, const void* k,
                     const int64_t* os, const int64_t* dqs, const int64_t* dks,
                     const void* mask, const int64_t* ms, float pdrop,
                     uint64_t seed, uint64_t offset, hipStream_t s);
+// delta[b, h, sq] = rowsum(dout * o) alone: the first kernel of the backward
+void flash_attn_bwd_delta(const void* dout, const void* o, float* delta,
+                          int64_t b, int64_t h, int64_t sq, int64_t dh,
+                          const int64_t* dos, const int64_t* os, hipStream_t s);
 
 // ---- dropout + residual add ------------------------------------------------
 // y = dropout(x, p) + residual; mask stored as uint8 per element

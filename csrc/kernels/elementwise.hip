@@ -67,12 +67,21 @@ __device__ __forceinline__ float silu_grad_f(float x) {
   return sig * (1.f + x * (1.f - sig));
 }
 
-template <int DT, bool FWD, int W>
+template <int DT, bool FWD, int W, bool BGRAD = false>
 __global__ void bias_gelu_kernel(const void* __restrict__ a, const void* __restrict__ x,
                                  const void* __restrict__ bias, void* __restrict__ out,
-                                 int64_t n, int64_t d) {
+                                 int64_t n, int64_t d, float* __restrict__ ws = nullptr) {
   // FWD: a == x (unused), out = gelu(x+bias).  BWD: a = dy, out = dx.
   // W=16: two 16B loads in flight per stream -- streaming-friendly MLP.
+  // BGRAD (backward, launched with gridDim*256*W % d == 0): the thread's W
+  // columns stay the same for its whole loop, so it sums the dx values it
+  // stores (as rounded to T) and writes its W partials to ws[thread*W];
+  // ws is then [gridDim*256*W/d, d], summed by ws_reduce.
+  float acc[W];
+  if (BGRAD) {
+#pragma unroll
+    for (int k = 0; k < W; ++k) acc[k] = 0.f;
+  }
   int64_t total = n * d;
   int64_t i0 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * W;
   int64_t stride = (int64_t)gridDim.x * blockDim.x * W;
@@ -92,10 +101,16 @@ __global__ void bias_gelu_kernel(const void* __restrict__ a, const void* __restr
     for (int k = 0; k < W; ++k) {
       float v = xf[k] + (bias ? bf[k] : 0.f);
       xf[k] = FWD ? gelu_f(v) : af[k] * gelu_grad_f(v);
+      if (BGRAD) acc[k] += (DT == kBF16) ? bf2f(f2bf(xf[k])) : xf[k];
     }
 #pragma unroll
     for (int v8 = 0; v8 < W / 8; ++v8)
       LS8<DT>::store8(out, i + 8 * v8, xf + 8 * v8);
+  }
+  if (BGRAD) {
+#pragma unroll
+    for (int v8 = 0; v8 < W / 8; ++v8)
+      LS8<kF32>::store8(ws, i0 + 8 * v8, acc + 8 * v8);
   }
 }
 
@@ -300,6 +315,41 @@ void bias_gelu_bwd(const void* dy, const void* x, const void* bias, void* dx,
     EDT(dtype,
         hipLaunchKernelGGL((bias_gelu_kernel<kBF16, false, 8>), g, dim3(256), 0, s, dy, x, bias, dx, n, d),
         hipLaunchKernelGGL((bias_gelu_kernel<kF32, false, 8>), g, dim3(256), 0, s, dy, x, bias, dx, n, d));
+  }
+}
+
+// Grid of the backward with the bias gradient fused: the smallest multiple
+// of q = d / gcd(d, 256*W) blocks that covers the elementwise grid, within
+// the elementwise cap (else the largest multiple below the cap).  0: no such
+// grid, the caller runs bias_gelu_bwd followed by colsum.
+static int64_t gcd64(int64_t a, int64_t b) { while (b) { int64_t t = a % b; a = b; b = t; } return a; }
+
+int bias_gelu_bwd_db_grid(int64_t n, int64_t d) {
+  if (d % 8 != 0 || n <= 0) return 0;
+  const int W = d % 16 == 0 ? 16 : 8;
+  const int64_t cap = elementwise_grid(1LL << 40);
+  const int64_t g0 = egrid(n * d / (W / 8)).x;
+  const int64_t q = d / gcd64(d, 256 * W);
+  if (q > cap) return 0;
+  int64_t g = (g0 + q - 1) / q * q;
+  if (g > cap) g = cap / q * q;
+  return (int)g;
+}
+
+void bias_gelu_bwd_db(const void* dy, const void* x, const void* bias, void* dx,
+                      float* db, float* ws, int grid, int64_t n, int64_t d,
+                      int dtype, hipStream_t s) {
+  dim3 g((unsigned)grid);
+  if (d % 16 == 0) {
+    EDT(dtype,
+        hipLaunchKernelGGL((bias_gelu_kernel<kBF16, false, 16, true>), g, dim3(256), 0, s, dy, x, bias, dx, n, d, ws),
+        hipLaunchKernelGGL((bias_gelu_kernel<kF32, false, 16, true>), g, dim3(256), 0, s, dy, x, bias, dx, n, d, ws));
+    ws_reduce(ws, db, nullptr, (int)((int64_t)grid * 256 * 16 / d), 1, d, s);
+  } else {
+    EDT(dtype,
+        hipLaunchKernelGGL((bias_gelu_kernel<kBF16, false, 8, true>), g, dim3(256), 0, s, dy, x, bias, dx, n, d, ws),
+        hipLaunchKernelGGL((bias_gelu_kernel<kF32, false, 8, true>), g, dim3(256), 0, s, dy, x, bias, dx, n, d, ws));
+    ws_reduce(ws, db, nullptr, (int)((int64_t)grid * 256 * 8 / d), 1, d, s);
   }
 }
 

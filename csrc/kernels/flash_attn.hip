@@ -273,25 +273,76 @@ __global__ void fa_bwd_delta_kernel(const short* __restrict__ dog, const short* 
                                     long long rows,
                                     long long do_sb, long long do_sh, long long do_ss,
                                     long long o_sb, long long o_sh, long long o_ss) {
-  long long wid = ((long long)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  int lane = threadIdx.x & 63;
-  long long nwaves = ((long long)gridDim.x * blockDim.x) >> 6;
-  for (long long r = wid; r < rows; r += nwaves) {
-    int sq = (int)(r % Sq);
-    int h = (int)((r / Sq) % H);
-    int b = (int)(r / ((long long)Sq * H));
-    const long long dob = b * do_sb + h * do_sh + sq * do_ss;
-    const long long ob = b * o_sb + h * o_sh + sq * o_ss;
-    float acc = 0.f;
-    for (int j = lane * 8; j < D; j += 64 * 8) {
-      shortx8 a = *reinterpret_cast<const shortx8*>(dog + dob + j);
-      shortx8 bb = *reinterpret_cast<const shortx8*>(og + ob + j);
+  // D/8 lanes per row (one 16 B load each), 256/(D/8) rows per block pass,
+  // 4 passes in flight.  Rows are walked in memory order: h fastest for the
+  // [B, S, H, D] strides of the packed-QKV / varlen paths (h_fast), s
+  // fastest for contiguous [B, H, S, D]; delta keeps its [B, H, Sq] order.
+  constexpr int LPR = D / 8, RPP = 256 / LPR, UNR = 4;
+  const int sub = threadIdx.x % LPR;
+  const int rin = threadIdx.x / LPR;
+  const bool h_fast = do_sh < do_ss;
+  for (long long r0 = (long long)blockIdx.x * (RPP * UNR); r0 < rows;
+       r0 += (long long)gridDim.x * (RPP * UNR)) {
+    shortx8 a[UNR], bb[UNR];
+    long long di[UNR];
 #pragma unroll
-      for (int k = 0; k < 8; ++k) acc += bf2f(a[k]) * bf2f(bb[k]);
+    for (int u = 0; u < UNR; ++u) {
+      const long long r = r0 + u * RPP + rin;
+      di[u] = -1;
+      if (r < rows) {
+        int sq, h, b;
+        if (h_fast) {
+          h = (int)(r % H);
+          sq = (int)((r / H) % Sq);
+        } else {
+          sq = (int)(r % Sq);
+          h = (int)((r / Sq) % H);
+        }
+        b = (int)(r / ((long long)Sq * H));
+        di[u] = ((long long)b * H + h) * Sq + sq;
+        a[u] = *reinterpret_cast<const shortx8*>(
+            dog + b * do_sb + h * do_sh + sq * do_ss + sub * 8);
+        bb[u] = *reinterpret_cast<const shortx8*>(
+            og + b * o_sb + h * o_sh + sq * o_ss + sub * 8);
+      }
     }
-    acc = wave_reduce(acc, SumOp());
-    if (lane == 0) delta[r] = acc;
+#pragma unroll
+    for (int u = 0; u < UNR; ++u) {
+      float acc = 0.f;
+      if (di[u] >= 0) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) acc += bf2f(a[u][k]) * bf2f(bb[u][k]);
+      }
+#pragma unroll
+      for (int off = LPR / 2; off > 0; off >>= 1) acc += __shfl_xor(acc, off, WAVE);
+      if (sub == 0 && di[u] >= 0) delta[di[u]] = acc;
+    }
   }
+}
+
+static void fa_bwd_delta(const void* dout, const void* o, float* delta,
+                         int64_t bh_h, int64_t sq, long long rows, int64_t dh,
+                         long long do_sb, long long do_sh, long long do_ss,
+                         long long o_sb, long long o_sh, long long o_ss,
+                         hipStream_t s) {
+  const int rows_per_iter = (256 / (int)(dh / 8)) * 4;
+  dim3 dgrid((unsigned)hmin<long long>(2048LL, (rows + rows_per_iter - 1) / rows_per_iter));
+  if (dh == 128)
+    hipLaunchKernelGGL((fa_bwd_delta_kernel<128>), dgrid, dim3(256), 0, s,
+                       (const short*)dout, (const short*)o, delta, (int)bh_h,
+                       (int)sq, rows, do_sb, do_sh, do_ss, o_sb, o_sh, o_ss);
+  else
+    hipLaunchKernelGGL((fa_bwd_delta_kernel<64>), dgrid, dim3(256), 0, s,
+                       (const short*)dout, (const short*)o, delta, (int)bh_h,
+                       (int)sq, rows, do_sb, do_sh, do_ss, o_sb, o_sh, o_ss);
+}
+
+// delta alone (tests / benchmarks); strides as in flash_attn_bwd
+void flash_attn_bwd_delta(const void* dout, const void* o, float* delta,
+                          int64_t b, int64_t h, int64_t sq, int64_t dh,
+                          const int64_t* dos, const int64_t* os, hipStream_t s) {
+  fa_bwd_delta(dout, o, delta, h, sq, b * h * sq, dh, dos[0], dos[1], dos[2],
+               os[0], os[1], os[2], s);
 }
 
 // ---------------------------------------------------------------------------
@@ -757,16 +808,8 @@ void flash_attn_bwd(const void* dout, const void* q, const void* k,
                     const int64_t* os, const int64_t* dqs, const int64_t* dks,
                     const void* mask, const int64_t* ms, float pdrop,
                     uint64_t seed, uint64_t offset, hipStream_t s) {
-  long long rows = b * h * sq;
-  dim3 dgrid((unsigned)hmin<long long>(2048LL, (rows + 3) / 4));
-  if (dh == 128)
-    hipLaunchKernelGGL((fa_bwd_delta_kernel<128>), dgrid, dim3(256), 0, s,
-                       (const short*)dout, (const short*)o, delta, (int)h,
-                       (int)sq, rows, dos[0], dos[1], dos[2], os[0], os[1], os[2]);
-  else
-    hipLaunchKernelGGL((fa_bwd_delta_kernel<64>), dgrid, dim3(256), 0, s,
-                       (const short*)dout, (const short*)o, delta, (int)h,
-                       (int)sq, rows, dos[0], dos[1], dos[2], os[0], os[1], os[2]);
+  fa_bwd_delta(dout, o, delta, h, sq, b * h * sq, dh, dos[0], dos[1], dos[2],
+               os[0], os[1], os[2], s);
 
   dim3 gkv((unsigned)(b * h), (unsigned)cdiv((int)skv, 128));
   dim3 gq((unsigned)cdiv((int)sq, 128), (unsigned)(b * h));
@@ -812,17 +855,9 @@ void flash_attn_varlen_bwd(const void* dout, const void* q, const void* k,
                            const int* kvbmap, float pdrop, uint64_t seed,
                            uint64_t offset, hipStream_t s) {
   // delta[h, total_q] = rowsum(do * o) over the packed [total, H, D] layout
-  long long rows = h * total_q;
-  dim3 dgrid((unsigned)hmin<long long>(2048LL, (rows + 3) / 4));
   const long long ss = h * dh;
-  if (dh == 128)
-    hipLaunchKernelGGL((fa_bwd_delta_kernel<128>), dgrid, dim3(256), 0, s,
-                       (const short*)dout, (const short*)o, delta, (int)h,
-                       (int)total_q, rows, 0, dh, ss, 0, dh, ss);
-  else
-    hipLaunchKernelGGL((fa_bwd_delta_kernel<64>), dgrid, dim3(256), 0, s,
-                       (const short*)dout, (const short*)o, delta, (int)h,
-                       (int)total_q, rows, 0, dh, ss, 0, dh, ss);
+  fa_bwd_delta(dout, o, delta, h, total_q, h * total_q, dh, 0, dh, ss, 0, dh,
+               ss, s);
   flash_attn_varlen_bwd32(dout, q, k, v, lse, delta, dq, dk, dv, h, total_q,
                           total_k, dh, scale, causal, nqblocks, nkvblocks,
                           cu_q, cu_k, qbmap, kvbmap, pdrop, seed, offset, s);

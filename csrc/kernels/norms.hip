@@ -3,8 +3,11 @@
 // Design (MI355X): these are HBM-bandwidth-bound at D=4096..8192; the
 // kernels do one vectorized pass per row (256-thread block per row,
 // 16B/lane loads), fp32 accumulation, wave64 shuffle + 4-slot LDS block
-// reduction.  dgamma/dbeta use a column-parallel kernel with one fp32
-// atomic per (column, row-chunk).
+// reduction.  Up to D = 8192 the residual add + LayerNorm forward and the
+// whole LayerNorm backward (dx, residual gradient, dgamma/dbeta) are
+// register-resident single passes (add_ln_fwd_kernel, ln_bwd_fused_kernel);
+// wider rows and RMSNorm use the per-row dx kernel plus a column-parallel
+// dgamma/dbeta kernel writing per-chunk partials for a reduce kernel.
 //
 // Reference behavior parity: paddle/phi/kernels/gpu/layer_norm_kernel.cu
 // (LayerNormFwdWithWelford) and rms_norm_kernel.cu (cuApplyRMSNorm) --
@@ -62,6 +65,78 @@ template <> struct VIO<kF32> {
 };
 
 // ---------------------------------------------------------------------------
+// Pinned row arithmetic.  Each LayerNorm pass exists twice -- the generic
+// kernel that re-reads the row and the register-resident fused kernel -- and
+// the two must agree bit for bit (tests/test_fused_passes_gpu.py).  Under
+// -ffast-math the compiler otherwise picks the summation tree and the fma
+// contractions per kernel, so the shared steps live in these helpers:
+// reassociation off, fused multiply-adds spelled out, and pin() where a
+// product must be rounded before its consumer.
+// ---------------------------------------------------------------------------
+// v, materialised in a VGPR: nothing contracts or reassociates through it
+__device__ __forceinline__ float pin(float v) {
+  asm("" : "+v"(v));
+  return v;
+}
+
+// Value as stored in T and read back.  bf16: the round trip.  fp32: pinned,
+// so that a following add is not contracted with the producing multiply.
+template <int DT>
+__device__ __forceinline__ float round_t(float v) {
+  if (DT == kBF16) return bf2f(f2bf(v));
+  return pin(v);
+}
+
+// K of the shifted moments: mean of the row's first 8 elements, summed left
+// to right.
+__device__ __forceinline__ float row_shift8(const float* f0) {
+#pragma clang fp reassociate(off)
+  float s = ((((((f0[0] + f0[1]) + f0[2]) + f0[3]) + f0[4]) + f0[5]) + f0[6]) + f0[7];
+  return s * 0.125f;
+}
+
+// forward moments of one element: sum += f, sumc += f-K, sumsq += (f-K)^2
+// with the square rounded before the add
+__device__ __forceinline__ void ln_moments(float f, float shift, float& sum,
+                                           float& sumc, float& sumsq) {
+  // reassociate(off): -ffast-math may otherwise fold the eight "- shift"
+  // into one "- 8*shift" after summing the raw values
+#pragma clang fp reassociate(off)
+  float c = f - shift;
+  sum += f;
+  sumc += c;
+  sumsq += pin(c * c);
+}
+
+// y = (f - mu) * rstd * w + b, evaluated as fma(w * rstd, f - mu, b)
+__device__ __forceinline__ float ln_y(float f, float mu, float rstd, float w, float b) {
+#pragma clang fp reassociate(off)
+  return __builtin_fmaf(pin(w * rstd), f - mu, b);
+}
+
+__device__ __forceinline__ float ln_xhat(float x, float mu, float rs) {
+  return pin((x - mu) * rs);
+}
+
+// backward row sums of one element: s1 += g*xhat, s2 += g, g = dy*w rounded
+__device__ __forceinline__ void ln_bwd_sums(float gy, float w, float xh,
+                                            float& s1, float& s2) {
+#pragma clang fp reassociate(off)
+  float g = pin(gy * w);
+  s1 = __builtin_fmaf(g, xh, s1);
+  s2 += g;
+}
+
+// dx = rs * (g - c2 - xhat * c1), c1 = mean(g*xhat), c2 = mean(g)
+__device__ __forceinline__ float ln_bwd_dx1(float gy, float w, float xh, float c1,
+                                            float c2, float rs) {
+#pragma clang fp reassociate(off)
+  float g = pin(gy * w);
+  float a = pin(g - c2);
+  return rs * __builtin_fmaf(-xh, c1, a);
+}
+
+// ---------------------------------------------------------------------------
 // LayerNorm forward: one 256-thread block per row.
 // ---------------------------------------------------------------------------
 template <int DT>
@@ -86,22 +161,14 @@ __global__ void ln_fwd_kernel(const void* __restrict__ x, const void* __restrict
     {
       float f0[8];
       VIO<DT>::load8(x, base, f0);
-      shift = ((f0[0] + f0[1]) + (f0[2] + f0[3]) + (f0[4] + f0[5]) + (f0[6] + f0[7])) * 0.125f;
+      shift = row_shift8(f0);
     }
     float sum = 0.f, sumc = 0.f, sumsq = 0.f;
     for (int64_t i = threadIdx.x * 8; i < d; i += blockDim.x * 8) {
       float f[8];
       VIO<DT>::load8(x, base + i, f);
 #pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        // -ffast-math may otherwise fold the eight "- shift" into one
-        // "- 8*shift" after summing the raw values
-#pragma clang fp reassociate(off)
-        float c = f[k] - shift;
-        sum += f[k];
-        sumc += c;
-        sumsq += c * c;
-      }
+      for (int k = 0; k < 8; ++k) ln_moments(f[k], shift, sum, sumc, sumsq);
     }
     float ts = block_reduce_256(sum, SumOp(), red, 0.f);
     float tsc = block_reduce_256(sumc, SumOp(), red + 4, 0.f);
@@ -118,7 +185,7 @@ __global__ void ln_fwd_kernel(const void* __restrict__ x, const void* __restrict
       if (b) VIO<DT>::load8(b, i, bf);
 #pragma unroll
       for (int k = 0; k < 8; ++k)
-        f[k] = (f[k] - mu) * rstd * wf[k] + (b ? bf[k] : 0.f);
+        f[k] = ln_y(f[k], mu, rstd, wf[k], b ? bf[k] : 0.f);
       VIO<DT>::store8(y, base + i, f);
     }
     __syncthreads();
@@ -142,28 +209,22 @@ __global__ void ln_bwd_dx_kernel(const void* __restrict__ dy, const void* __rest
       VIO<DT>::load8(x, base + i, xf);
       VIO<DT>::load8(w, i, wf);
 #pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        float g = gy[k] * wf[k];
-        float xh = (xf[k] - mu) * rs;
-        s1 += g * xh;
-        s2 += g;
-      }
+      for (int k = 0; k < 8; ++k)
+        ln_bwd_sums(gy[k], wf[k], ln_xhat(xf[k], mu, rs), s1, s2);
     }
     float t1 = block_reduce_256(s1, SumOp(), red, 0.f);
     __syncthreads();
     float t2 = block_reduce_256(s2, SumOp(), red + 4, 0.f);
     const float inv_d = 1.f / d;
+    const float c1 = pin(t1 * inv_d), c2 = pin(t2 * inv_d);
     for (int64_t i = threadIdx.x * 8; i < d; i += blockDim.x * 8) {
       float gy[8], xf[8], wf[8];
       VIO<DT>::load8(dy, base + i, gy);
       VIO<DT>::load8(x, base + i, xf);
       VIO<DT>::load8(w, i, wf);
 #pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        float g = gy[k] * wf[k];
-        float xh = (xf[k] - mu) * rs;
-        gy[k] = rs * (g - t2 * inv_d - xh * t1 * inv_d);
-      }
+      for (int k = 0; k < 8; ++k)
+        gy[k] = ln_bwd_dx1(gy[k], wf[k], ln_xhat(xf[k], mu, rs), c1, c2, rs);
       VIO<DT>::store8(dx, base + i, gy);
     }
     __syncthreads();
@@ -228,6 +289,179 @@ __global__ void ln_bwd_dwdb_kernel(const void* __restrict__ dy, const void* __re
       atomicAdd(&dw[c0 + k], aw[k]);
       if (db) atomicAdd(&db[c0 + k], ab[k]);
     }
+}
+
+// ---------------------------------------------------------------------------
+// Fused residual add + LayerNorm forward: h = x + residual (stored in T),
+// y = LN(h) from the stored h.  Thread t owns the 8-wide column strips
+// t*8 + j*2048, j < NS (d <= NS*2048), and keeps its slice of h in
+// registers, so h is written once and never read back.  Sums run in the
+// order of ln_fwd_kernel: y / mean / rstd are bit-equal to
+// dropout_add_fwd(p=0) followed by ln_fwd_kernel.
+// ---------------------------------------------------------------------------
+template <int DT, int NS>
+__global__ __launch_bounds__(256) void add_ln_fwd_kernel(
+    const void* __restrict__ x, const void* __restrict__ res,
+    const void* __restrict__ w, const void* __restrict__ b,
+    void* __restrict__ h, void* __restrict__ y, float* __restrict__ mean_out,
+    float* __restrict__ rstd_out, int64_t n, int64_t d, float eps) {
+  __shared__ float red[12];
+  const int64_t c0 = threadIdx.x * 8;
+  for (int64_t row = blockIdx.x; row < n; row += gridDim.x) {
+    const int64_t base = row * d;
+    float shift;
+    {
+      float f0[8], r0[8];
+      VIO<DT>::load8(x, base, f0);
+      VIO<DT>::load8(res, base, r0);
+#pragma unroll
+      for (int k = 0; k < 8; ++k) f0[k] = round_t<DT>(f0[k] + r0[k]);
+      shift = row_shift8(f0);
+    }
+    float hf[NS][8];
+    float sum = 0.f, sumc = 0.f, sumsq = 0.f;
+#pragma unroll
+    for (int j = 0; j < NS; ++j) {
+      const int64_t c = c0 + (int64_t)j * 2048;
+      if (c < d) {
+        float rf[8];
+        VIO<DT>::load8(x, base + c, hf[j]);
+        VIO<DT>::load8(res, base + c, rf);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) hf[j][k] = round_t<DT>(hf[j][k] + rf[k]);
+        VIO<DT>::store8(h, base + c, hf[j]);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) ln_moments(hf[j][k], shift, sum, sumc, sumsq);
+      }
+    }
+    float ts = block_reduce_256(sum, SumOp(), red, 0.f);
+    float tsc = block_reduce_256(sumc, SumOp(), red + 4, 0.f);
+    float tss = block_reduce_256(sumsq, SumOp(), red + 8, 0.f);
+    float mu = ts / d;
+    float dmu = tsc / d;
+    float var = fmaxf(tss / d - dmu * dmu, 0.f);
+    float rstd = rsqrtf(var + eps);
+    if (threadIdx.x == 0) { mean_out[row] = mu; rstd_out[row] = rstd; }
+#pragma unroll
+    for (int j = 0; j < NS; ++j) {
+      const int64_t c = c0 + (int64_t)j * 2048;
+      if (c < d) {
+        float wf[8], bf[8], f[8];
+        VIO<DT>::load8(w, c, wf);
+        if (b) VIO<DT>::load8(b, c, bf);
+#pragma unroll
+        for (int k = 0; k < 8; ++k)
+          f[k] = ln_y(hf[j][k], mu, rstd, wf[k], b ? bf[k] : 0.f);
+        VIO<DT>::store8(y, base + c, f);
+      }
+    }
+    __syncthreads();
+  }
+}
+
+// ---------------------------------------------------------------------------
+// One-pass LayerNorm backward: dx (+ optional residual gradient) and the
+// dw/db partials from a single read of dy and x.  Column ownership as in
+// add_ln_fwd_kernel; the thread keeps dy and xhat of the row in registers
+// between the row sums and the dx pass, and accumulates dy*xhat / dy of its
+// own columns over all rows of the block.  The block's partials go to
+// ws[blockIdx.x][2][d] with plain stores; ws_reduce_kernel sums them.
+// The row sums s1 / s2 run in the order of ln_bwd_dx_kernel.
+// dres: dx = round_T(round_T(LN term) + dres), i.e. what ln_bwd_dx_kernel
+// followed by a tensor add in T gives.
+// ---------------------------------------------------------------------------
+template <int DT, int NS, bool HAS_DRES>
+__global__ __launch_bounds__(256) void ln_bwd_fused_kernel(
+    const void* __restrict__ dy, const void* __restrict__ x,
+    const void* __restrict__ w, const float* __restrict__ mean,
+    const float* __restrict__ rstd, const void* __restrict__ dres,
+    void* __restrict__ dx, float* __restrict__ ws, int64_t n, int64_t d) {
+  __shared__ float red[8];
+  const int64_t c0 = threadIdx.x * 8;
+  float wf[NS][8], aw[NS][8], ab[NS][8];
+#pragma unroll
+  for (int j = 0; j < NS; ++j) {
+    const int64_t c = c0 + (int64_t)j * 2048;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) { wf[j][k] = 0.f; aw[j][k] = 0.f; ab[j][k] = 0.f; }
+    if (c < d) VIO<DT>::load8(w, c, wf[j]);
+  }
+  for (int64_t row = blockIdx.x; row < n; row += gridDim.x) {
+    const int64_t base = row * d;
+    const float mu = mean[row], rs = rstd[row];
+    float gy[NS][8], xh[NS][8];
+    float s1 = 0.f, s2 = 0.f;  // sum(g*xhat), sum(g)
+#pragma unroll
+    for (int j = 0; j < NS; ++j) {
+      const int64_t c = c0 + (int64_t)j * 2048;
+      if (c < d) {
+        VIO<DT>::load8(dy, base + c, gy[j]);
+        VIO<DT>::load8(x, base + c, xh[j]);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+          xh[j][k] = ln_xhat(xh[j][k], mu, rs);
+          ln_bwd_sums(gy[j][k], wf[j][k], xh[j][k], s1, s2);
+        }
+      }
+    }
+    float t1 = block_reduce_256(s1, SumOp(), red, 0.f);
+    __syncthreads();
+    float t2 = block_reduce_256(s2, SumOp(), red + 4, 0.f);
+    const float inv_d = 1.f / d;
+    const float c1 = pin(t1 * inv_d), c2 = pin(t2 * inv_d);
+#pragma unroll
+    for (int j = 0; j < NS; ++j) {
+      const int64_t c = c0 + (int64_t)j * 2048;
+      if (c < d) {
+        float o[8], rf[8];
+        if (HAS_DRES) VIO<DT>::load8(dres, base + c, rf);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+          o[k] = ln_bwd_dx1(gy[j][k], wf[j][k], xh[j][k], c1, c2, rs);
+          if (HAS_DRES) o[k] = round_t<DT>(o[k]) + rf[k];
+          aw[j][k] += gy[j][k] * xh[j][k];
+          ab[j][k] += gy[j][k];
+        }
+        VIO<DT>::store8(dx, base + c, o);
+      }
+    }
+    __syncthreads();
+  }
+  float* wrow = ws + (int64_t)blockIdx.x * 2 * d;
+#pragma unroll
+  for (int j = 0; j < NS; ++j) {
+    const int64_t c = c0 + (int64_t)j * 2048;
+    if (c < d) {
+      VIO<kF32>::store8(wrow, c, aw[j]);
+      VIO<kF32>::store8(wrow, d + c, ab[j]);
+    }
+  }
+}
+
+// Sum partials ws[parts][nout][d] over parts -> out[o][d], o = blockIdx.y.
+// 1024 threads: wave v adds parts v, v+16, ... for 64 columns (256 B per
+// load), the 16 wave sums meet in LDS and are added in wave order, so the
+// result does not depend on scheduling.  d/64 x nout blocks keep every CU
+// busy where a serial walk on d/256 blocks would not.
+__global__ __launch_bounds__(1024) void ws_reduce_kernel(
+    const float* __restrict__ ws, float* __restrict__ out0,
+    float* __restrict__ out1, int parts, int nout, int64_t d) {
+  __shared__ float lds[16][64];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int64_t c = (int64_t)blockIdx.x * 64 + lane;
+  const int o = blockIdx.y;
+  float acc = 0.f;
+  if (c < d)
+    for (int p = wv; p < parts; p += 16)
+      acc += ws[((int64_t)p * nout + o) * d + c];
+  lds[wv][lane] = acc;
+  __syncthreads();
+  if (wv == 0 && c < d) {
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) s += lds[i][lane];
+    (o == 0 ? out0 : out1)[c] = s;
+  }
 }
 
 // reduce [2*chunks, d] partials -> dw[d], db[d]
@@ -367,6 +601,55 @@ void layer_norm_bwd_dwdb(const void* dy, const void* x, const float* mean,
   if (ws)
     hipLaunchKernelGGL(dwdb_reduce_kernel, dim3((unsigned)cdiv((int)d, 256)),
                        dim3(256), 0, s, ws, dw, db, chunks, d);
+}
+
+// strip count of the register-resident kernels: 1..4 for d <= 8192
+#define NS_SWITCH(d, ...)                                            \
+  switch (cdiv((int)(d), 2048)) {                                    \
+    case 1: { constexpr int NS = 1; __VA_ARGS__; break; }            \
+    case 2: { constexpr int NS = 2; __VA_ARGS__; break; }            \
+    case 3: { constexpr int NS = 3; __VA_ARGS__; break; }            \
+    default: { constexpr int NS = 4; __VA_ARGS__; break; }           \
+  }
+
+bool ln_fused_ok(int64_t d) { return d % 8 == 0 && d <= kLnFusedMaxD; }
+
+int ln_bwd_fused_grid(int64_t n, int cap) {
+  if (cap <= 0) cap = kLnBwdGridCap;
+  return (int)hmin<int64_t>(n, cap);
+}
+
+void ws_reduce(const float* ws, float* out0, float* out1, int parts, int nout,
+               int64_t d, hipStream_t s) {
+  dim3 grid((unsigned)((d + 63) / 64), out1 ? 2 : 1);
+  hipLaunchKernelGGL(ws_reduce_kernel, grid, dim3(1024), 0, s, ws, out0, out1,
+                     parts, nout, d);
+}
+
+void add_layer_norm_fwd(const void* x, const void* residual, const void* w,
+                        const void* b, void* h, void* y, float* mean,
+                        float* rstd, int64_t n, int64_t d, float eps, int dtype,
+                        hipStream_t s) {
+  DT_SWITCH(dtype, NS_SWITCH(d, hipLaunchKernelGGL(
+      (add_ln_fwd_kernel<DT, NS>), dim3(norm_grid(n)), dim3(256), 0, s, x,
+      residual, w, b, h, y, mean, rstd, n, d, eps)));
+}
+
+void layer_norm_bwd_fused(const void* dy, const void* x, const void* w,
+                          const float* mean, const float* rstd,
+                          const void* dres, void* dx, float* dw, float* db,
+                          float* ws, int grid, int64_t n, int64_t d, int dtype,
+                          hipStream_t s) {
+  if (dres) {
+    DT_SWITCH(dtype, NS_SWITCH(d, hipLaunchKernelGGL(
+        (ln_bwd_fused_kernel<DT, NS, true>), dim3(grid), dim3(256), 0, s, dy, x,
+        w, mean, rstd, dres, dx, ws, n, d)));
+  } else {
+    DT_SWITCH(dtype, NS_SWITCH(d, hipLaunchKernelGGL(
+        (ln_bwd_fused_kernel<DT, NS, false>), dim3(grid), dim3(256), 0, s, dy, x,
+        w, mean, rstd, dres, dx, ws, n, d)));
+  }
+  ws_reduce(ws, dw, db, grid, 2, d, s);
 }
 
 void rms_norm_fwd(const void* x, const void* residual, const void* w, void* y,

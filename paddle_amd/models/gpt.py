@@ -131,9 +131,42 @@ class GPTDecoderLayer(nn.Layer):
         self.mlp = GPTMLP(cfg)
         self.dropout = cfg.hidden_dropout
 
-    def forward(self, x):
-        h = hot.dropout_add(self.attn(self.ln1(x)), x, self.dropout, self.training)
-        return hot.dropout_add(self.mlp(self.ln2(h)), h, self.dropout, self.training)
+    def _add_ln(self, x, residual, ln):
+        return hot.add_layer_norm(x, residual, ln.weight, ln.bias, ln._epsilon,
+                                  self.dropout, self.training)
+
+    def forward(self, x, residual=None, defer_add=False):
+        """layer(x) is the plain block.  The residual adds are fused into
+        the LayerNorm that follows them: ln2 with the attention add, and --
+        when the caller chains layers -- ln1 with the previous layer's MLP
+        add: `residual` given means the block input is x + residual (the
+        pair a defer_add=True layer returned), and defer_add=True returns
+        (mlp_out, h) with the last add left to the next norm."""
+        if residual is None:
+            y = self.ln1(x)
+        else:
+            x, y = self._add_ln(x, residual, self.ln1)
+        h, y = self._add_ln(self.attn(y), x, self.ln2)
+        m = self.mlp(y)
+        if defer_add:
+            return m, h
+        return hot.dropout_add(m, h, self.dropout, self.training)
+
+
+class GPTFinalNorm(nn.LayerNorm):
+    """LayerNorm that can take the last layer's deferred (mlp_out, h) pair.
+    The add runs inside this module's forward, so per-module hooks (ZeRO-3
+    parameter gathers) see the parameters used where they are bound."""
+
+    def __init__(self, cfg: GPTConfig):
+        super().__init__(cfg.hidden_size)
+        self.dropout = cfg.hidden_dropout
+
+    def forward(self, x, residual=None):
+        if residual is None:
+            return super().forward(x)
+        return hot.add_layer_norm(x, residual, self.weight, self.bias,
+                                  self._epsilon, self.dropout, self.training)[1]
 
 
 class GPTModel(nn.Layer):
@@ -142,19 +175,21 @@ class GPTModel(nn.Layer):
         self.cfg = cfg
         self.embeddings = GPTEmbeddings(cfg)
         self.layers = nn.LayerList([GPTDecoderLayer(cfg) for _ in range(cfg.num_layers)])
-        self.final_norm = nn.LayerNorm(cfg.hidden_size)
+        self.final_norm = GPTFinalNorm(cfg)
 
     def forward(self, input_ids, position_ids=None):
         x = self.embeddings(input_ids, position_ids)
-        use_rc = self.cfg.use_recompute and self.training
-        if use_rc:
+        if self.cfg.use_recompute and self.training:
+            # recompute keeps the plain one-tensor form
             from ..distributed.fleet.recompute import recompute
+            for layer in self.layers:
+                x = recompute(layer, x) if x.requires_grad else layer(x)
+            return self.final_norm(x)
+        # each layer hands (mlp_out, h) on; the add happens in the next norm
+        res = None
         for layer in self.layers:
-            if use_rc and x.requires_grad:
-                x = recompute(layer, x)
-            else:
-                x = layer(x)
-        return self.final_norm(x)
+            x, res = layer(x, res, defer_add=True)
+        return self.final_norm(x, res)
 
 
 class GPTForPretraining(nn.Layer):

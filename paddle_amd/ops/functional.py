@@ -188,6 +188,92 @@ def layer_norm(x, weight, bias=None, epsilon=1e-5):
 
 
 # ---------------------------------------------------------------------------
+# residual add + layer_norm in one pass: h = x + residual, y = LN(h)
+# ---------------------------------------------------------------------------
+def _add_ln_native_ok(x, residual, w, b=None, p=0.0, training=True):
+    """Fused add + layer_norm: x and residual of one dtype and shape, both
+    contiguous, and dropout inactive (p == 0 or eval)."""
+    if p != 0 and training:
+        return False
+    if not (isinstance(x, torch.Tensor) and isinstance(residual, torch.Tensor)):
+        return False
+    return _kernel_ok(x, last_mult=8, same=(residual,), vecs=(w, b),
+                      contiguous=(x, residual))
+
+
+class _AddLayerNorm(torch.autograd.Function):
+    """(h, y) = (x + residual, layer_norm(x + residual)).  The backward
+    hands the gradient arriving at h to the layer_norm backward kernel as
+    dres, so neither direction spends a pass on the add.  Off the GPU it
+    composes the reference formulas of _DropoutAdd(p=0) and _LayerNorm."""
+
+    @staticmethod
+    def forward(ctx, x, residual, w, b, eps):
+        ctx.set_materialize_grads(False)
+        ctx.native = _ext.use_native(x)
+        ctx.w_dtype = w.dtype
+        ctx.b_dtype = b.dtype if b is not None else w.dtype
+        ctx.has_bias = b is not None
+        if ctx.native:
+            C = _ext.get_ext()
+            w = _as_dtype(w, x.dtype)
+            h, y, mean, rstd = C.add_layer_norm_fwd(x, residual, w,
+                                                    _as_dtype(b, x.dtype), eps)
+        else:
+            h = x.clone() + residual
+            hf = h.float()
+            mean = hf.mean(-1).reshape(-1)
+            var = hf.var(-1, unbiased=False).reshape(-1)
+            rstd = torch.rsqrt(var + eps)
+            xhat = (hf - mean.view(*h.shape[:-1], 1)) * rstd.view(*h.shape[:-1], 1)
+            y = xhat * w.float() + (b.float() if b is not None else 0.0)
+            y = y.to(h.dtype)
+        ctx.save_for_backward(h, w, mean, rstd)
+        return h, y
+
+    @staticmethod
+    def backward(ctx, dh, dy):
+        if dy is None:
+            return dh, dh, None, None, None
+        h, w, mean, rstd = ctx.saved_tensors
+        if ctx.native:
+            C = _ext.get_ext()
+            dres = None if dh is None else dh.to(h.dtype).contiguous()
+            dx, dw, db = C.layer_norm_bwd(dy.to(h.dtype).contiguous(), h, w,
+                                          mean, rstd, ctx.has_bias, dres)
+            dw, db = dw.to(ctx.w_dtype), db.to(ctx.b_dtype)
+        else:
+            d = h.shape[-1]
+            hf = h.float()
+            dyf = dy.float()
+            mu = mean.view(*h.shape[:-1], 1)
+            rs = rstd.view(*h.shape[:-1], 1)
+            xhat = (hf - mu) * rs
+            g = dyf * w.float()
+            s1 = (g * xhat).mean(-1, keepdim=True)
+            s2 = g.mean(-1, keepdim=True)
+            dx = (rs * (g - s2 - xhat * s1)).to(h.dtype)
+            if dh is not None:
+                dx = dx + dh
+            dw = (dyf * xhat).reshape(-1, d).sum(0).to(w.dtype)
+            db = dyf.reshape(-1, d).sum(0).to(ctx.b_dtype)
+        return dx, dx, dw, (db if ctx.has_bias else None), None
+
+
+def add_layer_norm(x, residual, weight, bias=None, epsilon=1e-5, p=0.0,
+                   training=True):
+    """(h, y) with h = dropout(x, p) + residual and y = layer_norm(h).  One
+    kernel each way when dropout is inactive and the operands fit the
+    kernel contract; otherwise exactly dropout_add followed by layer_norm
+    (CPU, tracing, mixed dtypes under amp.auto_cast, p > 0)."""
+    if (not _tracing() and _add_ln_native_ok(x, residual, weight, bias, p, training)
+            and _ext.use_native(x)):
+        return _AddLayerNorm.apply(x, residual, weight, bias, epsilon)
+    h = dropout_add(x, residual, p, training)
+    return h, layer_norm(h, weight, bias, epsilon)
+
+
+# ---------------------------------------------------------------------------
 # rms_norm (+ optional fused residual add)
 # paddle parity: incubate/nn/functional/fused_rms_norm.py, rms_norm_kernel.cu
 # ---------------------------------------------------------------------------
@@ -361,6 +447,12 @@ def softmax_cross_entropy(logits, labels, ignore_index=-100, reduction="none"):
 # ---------------------------------------------------------------------------
 # bias + gelu (fused_bias_act parity; erf gelu)
 # ---------------------------------------------------------------------------
+# Below this many elements dx is still L2-resident when colsum re-reads it,
+# so the fused bias gradient saves no HBM pass: small calls keep the dx
+# kernel followed by colsum.
+_BIAS_GELU_DB_FUSE_MIN = 1 << 20
+
+
 class _BiasGelu(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, bias):
@@ -380,9 +472,17 @@ class _BiasGelu(torch.autograd.Function):
         # d/dx gelu(x+b) == d/db gelu(x+b), so db = colsum(dx)
         if ctx.native:
             C = _ext.get_ext()
-            dx = C.bias_gelu_bwd(dy.to(x.dtype).contiguous(), x.contiguous(),
-                                 _as_dtype(b, x.dtype))
-            db = C.colsum(dx).to(b.dtype) if ctx.has_bias else None
+            if ctx.has_bias and x.numel() >= _BIAS_GELU_DB_FUSE_MIN:
+                # db summed inside the dx kernel (where no grid keeps a
+                # thread on its columns the binding itself runs the dx
+                # kernel, then colsum)
+                dx, db = C.bias_gelu_bwd_db(dy.to(x.dtype).contiguous(),
+                                            x.contiguous(), _as_dtype(b, x.dtype))
+                db = db.to(b.dtype)
+            else:
+                dx = C.bias_gelu_bwd(dy.to(x.dtype).contiguous(), x.contiguous(),
+                                     _as_dtype(b, x.dtype))
+                db = C.colsum(dx).to(b.dtype) if ctx.has_bias else None
         else:
             v = x.float() + (b.float() if b is not None else 0.0)
             cdf = 0.5 * (1.0 + torch.erf(v * 0.7071067811865476))

@@ -64,6 +64,50 @@ r = torch.randn(M, H, device=DEV, dtype=torch.bfloat16)
 t = timeit(lambda: C.dropout_add_fwd(x, r, 0.1, 1234, 0))
 report("dropout_add fwd [16k,4k]", t, 3 * M * H * 2 / GB)
 
+# ---- fused passes at the flagship shapes: tokens = 12*2048 -----------------
+# bytes = the minimum each kernel has to move (bf16 tensors, fp32 partials
+# not counted)
+M2 = 12 * 2048
+del z, dy, x, dyh, r, y
+x = torch.randn(M2, H, device=DEV, dtype=torch.bfloat16)
+r = torch.randn(M2, H, device=DEV, dtype=torch.bfloat16)
+dyh = torch.randn(M2, H, device=DEV, dtype=torch.bfloat16)
+T1 = M2 * H * 2 / GB   # one [24576, 4096] bf16 tensor
+
+t = timeit(lambda: (C.dropout_add_fwd(x, r, 0.0, 0, 0), C.layer_norm_fwd(x, w, bb, 1e-5)))
+report("add, ln fwd (2 kernels)", t, 5 * T1)
+t = timeit(lambda: C.add_layer_norm_fwd(x, r, w, bb, 1e-5))
+report("add_ln fwd [24k,4k]", t, 4 * T1)
+
+_, mean, rstd = C.layer_norm_fwd(x, w, bb, 1e-5)
+t = timeit(lambda: C.layer_norm_bwd(dyh, x, w, mean, rstd, True, None, False).__getitem__(0).add_(r))
+report("ln bwd 2-kernel + add", t, 8 * T1)
+t = timeit(lambda: C.layer_norm_bwd(dyh, x, w, mean, rstd, True, None, False))
+report("ln bwd 2-kernel", t, 5 * T1)
+for cap in (256, 512, 1024, 2048):
+    t = timeit(lambda: C.layer_norm_bwd(dyh, x, w, mean, rstd, True, r, True, cap))
+    report(f"ln bwd 1-pass+dres G={cap}", t, 4 * T1)
+t = timeit(lambda: C.layer_norm_bwd(dyh, x, w, mean, rstd, True))
+report("ln bwd 1-pass (default G)", t, 3 * T1)
+
+qkv_do = torch.randn(12, 2048, 32, 128, device=DEV, dtype=torch.bfloat16).permute(0, 2, 1, 3)
+qkv_o = torch.randn(12, 2048, 32, 128, device=DEV, dtype=torch.bfloat16).permute(0, 2, 1, 3)
+t = timeit(lambda: C.flash_attn_bwd_delta(qkv_do, qkv_o))
+report("fa_bwd delta packed [24k,4k]", t, 2 * T1)
+do_c, o_c = qkv_do.contiguous(), qkv_o.contiguous()
+t = timeit(lambda: C.flash_attn_bwd_delta(do_c, o_c))
+report("fa_bwd delta contiguous", t, 2 * T1)
+del qkv_do, qkv_o, do_c, o_c, x, r, dyh
+
+z = torch.randn(M2, F, device=DEV, dtype=torch.bfloat16)
+dy = torch.randn(M2, F, device=DEV, dtype=torch.bfloat16)
+T4 = M2 * F * 2 / GB
+t = timeit(lambda: C.bias_gelu_bwd_db(dy, z, b, False))
+report("bias_gelu bwd, colsum", t, 4 * T4)
+t = timeit(lambda: C.bias_gelu_bwd_db(dy, z, b))
+report("bias_gelu bwd+db [24k,16k]", t, 3 * T4)
+del z, dy
+
 g = torch.randn(M, device=DEV)
 n = 201 * 2 ** 20
 master = torch.randn(n, device=DEV)
