@@ -850,32 +850,87 @@ Tensor decode_gemm(const Tensor& x, const Tensor& w,
   return y;
 }
 
+// Contract of the MFMA W-streamer (decode_stream_kernel, docs/KERNELS.md),
+// shared by decode_gemm_mfma / _int8 / _int4: every lane does 16-byte loads
+// of whole 64 x 256 weight tiles and of x rows, so shapes, placement and base
+// alignment are checked here, before any launch.  The callers check what is
+// specific to their weight format first; `k` is the K their weight holds,
+// `kdesc` names it in the message.  Allocates the split-K workspace and y.
+struct DecodeStreamCall {
+  int64_t m, n, k;
+  const void* bias;
+  Tensor ws, y;
+};
+
+static bool aligned16(const Tensor& t) {
+  return reinterpret_cast<uintptr_t>(t.const_data_ptr()) % 16 == 0;
+}
+
+static DecodeStreamCall check_decode_stream(const char* op, const Tensor& x,
+                                            const Tensor& w, int64_t k,
+                                            const char* kdesc,
+                                            const c10::optional<Tensor>& bias,
+                                            int64_t ksplit) {
+  CHECK_IN(x);
+  TORCH_CHECK(x.dim() == 2 && x.scalar_type() == torch::kBFloat16, op,
+              ": x must be a 2-D bf16 tensor");
+  TORCH_CHECK(w.device() == x.device(), op, ": weight and x must be on one device");
+  const int64_t m = x.size(0), n = w.size(1);
+  TORCH_CHECK(x.size(1) == k, op, ": ", kdesc, " must equal K");
+  TORCH_CHECK(m >= 1 && m <= 32, op, ": 1 <= M <= 32, got ", m);
+  TORCH_CHECK(n > 0 && n % 256 == 0, op, ": N % 256 == 0, got ", n);
+  TORCH_CHECK(k > 0 && k % 64 == 0 && k <= (int64_t(1) << 24), op,
+              ": K % 64 == 0 (and K <= 2^24), got ", k);
+  TORCH_CHECK(aligned16(x) && aligned16(w), op,
+              ": x and weight data must be 16-byte aligned");
+  TORCH_CHECK(ksplit >= 0, op, ": ksplit >= 0");
+  const void* bp = nullptr;
+  if (bias.has_value()) {
+    TORCH_CHECK(bias->is_cuda() && bias->is_contiguous() &&
+                bias->scalar_type() == torch::kBFloat16 && bias->numel() == n,
+                op, ": bias must be contiguous bf16 with N elements");
+    bp = bias->const_data_ptr();
+  }
+  const int64_t splits = pa::decode_split_plan(k, n, ksplit).splits;
+  const int64_t mt = m <= 16 ? 16 : 32;
+  return {m, n, k, bp,
+          torch::empty({splits, mt, n}, x.options().dtype(torch::kFloat)),
+          torch::empty({m, n}, x.options())};
+}
+
+Tensor decode_gemm_mfma(const Tensor& x, const Tensor& w,
+                        const c10::optional<Tensor>& bias) {
+  const char* op = "decode_gemm_mfma";
+  TORCH_CHECK(w.is_cuda() && w.dim() == 2 && w.scalar_type() == torch::kBFloat16,
+              op, ": w must be a 2-D bf16 GPU tensor");
+  TORCH_CHECK(w.stride(1) == 1 && w.stride(0) % 8 == 0, op,
+              ": w must have unit column stride and a row stride % 8 == 0");
+  auto c = check_decode_stream(op, x, w, w.size(0), "w.size(0)", bias, 0);
+  pa::decode_gemm_mfma(x.const_data_ptr(), w.const_data_ptr(), c.bias,
+                       c.y.mutable_data_ptr(), c.ws.mutable_data_ptr<float>(),
+                       c.m, c.n, c.k, w.stride(0), 0, cur_stream());
+  return c.y;
+}
+
+// qw int8 [K, N] contiguous, scale fp32 [N] (weight_quantize, int8)
 Tensor decode_gemm_int8(const Tensor& x, const Tensor& qw,
                         const Tensor& scale,
                         const c10::optional<Tensor>& bias) {
-  CHECK_IN(x);
-  TORCH_CHECK(x.dim() == 2 && qw.dim() == 2 && qw.is_contiguous());
-  TORCH_CHECK(x.scalar_type() == torch::kBFloat16 &&
-              qw.scalar_type() == torch::kChar &&
-              scale.scalar_type() == torch::kFloat);
-  int64_t m = x.size(0), k = x.size(1), n = qw.size(1);
-  TORCH_CHECK(qw.size(0) == k && m <= 32 && n % 256 == 0 && k % 64 == 0);
-  TORCH_CHECK(scale.numel() == n);
-  int64_t nblk = n / 256;
-  // fp32 partials cost ksplit*M*N*8 B of traffic -- cap harder (see the
-  // bf16 binding's note; the reduce was 13% of serving kernel time)
-  int64_t kmin = nblk <= 24 ? 256 : 512;
-  int64_t ksplit = std::min<int64_t>(std::max<int64_t>(1, 1024 / nblk),
-                                     std::max<int64_t>(1, k / kmin));
-  int64_t mt = m <= 16 ? 16 : 32;
-  auto ws = torch::empty({ksplit, mt, n}, x.options().dtype(torch::kFloat));
-  auto y = torch::empty({m, n}, x.options());
-  pa::decode_gemm_mfma(x.const_data_ptr(), qw.const_data_ptr(),
-                       bias.has_value() ? bias->const_data_ptr() : nullptr,
-                       y.mutable_data_ptr(), ws.mutable_data_ptr<float>(), m,
-                       n, k, n, ksplit, cur_stream(),
-                       scale.const_data_ptr<float>(), true);
-  return y;
+  const char* op = "decode_gemm_int8";
+  TORCH_CHECK(qw.is_cuda() && scale.is_cuda(), op, ": qw and scale must be GPU tensors");
+  TORCH_CHECK(qw.dim() == 2 && qw.is_contiguous(), op,
+              ": qw must be a contiguous [K, N] tensor");
+  TORCH_CHECK(qw.scalar_type() == torch::kChar, op, ": qw must be int8");
+  TORCH_CHECK(scale.scalar_type() == torch::kFloat && scale.is_contiguous(),
+              op, ": scale must be contiguous fp32");
+  TORCH_CHECK(scale.dim() == 1 && scale.size(0) == qw.size(1), op,
+              ": per-channel scale must be [N]");
+  auto c = check_decode_stream(op, x, qw, qw.size(0), "qw.size(0)", bias, 0);
+  pa::decode_gemm_int8(x.const_data_ptr(), qw.const_data_ptr(),
+                       scale.const_data_ptr<float>(), c.bias,
+                       c.y.mutable_data_ptr(), c.ws.mutable_data_ptr<float>(),
+                       c.m, c.n, c.k, 0, cur_stream());
+  return c.y;
 }
 
 // int4 weight-only storage shared by decode_gemm_int4 and dequant_int4:
@@ -906,42 +961,14 @@ static int64_t check_int4_weight(const Tensor& qw, const Tensor& scale,
 Tensor decode_gemm_int4(const Tensor& x, const Tensor& qw, const Tensor& scale,
                         const c10::optional<Tensor>& bias, int64_t group_size,
                         int64_t ksplit) {
-  CHECK_IN(x);
-  TORCH_CHECK(x.dim() == 2 && x.scalar_type() == torch::kBFloat16,
-              "decode_gemm_int4: x must be a 2-D bf16 tensor");
-  const int64_t k = check_int4_weight(qw, scale, group_size, "decode_gemm_int4");
-  const int64_t m = x.size(0), n = qw.size(1);
-  TORCH_CHECK(x.size(1) == k, "decode_gemm_int4: qw.size(0)*2 must equal K");
-  TORCH_CHECK(m >= 1 && m <= 32, "decode_gemm_int4: 1 <= M <= 32, got ", m);
-  TORCH_CHECK(n > 0 && n % 256 == 0, "decode_gemm_int4: N % 256 == 0, got ", n);
-  TORCH_CHECK(k > 0 && k % 64 == 0 && k <= (int64_t(1) << 24),
-              "decode_gemm_int4: K % 64 == 0 (and K <= 2^24), got ", k);
-  TORCH_CHECK(ksplit >= 0, "decode_gemm_int4: ksplit >= 0");
-  const void* bp = nullptr;
-  if (bias.has_value()) {
-    TORCH_CHECK(bias->is_cuda() && bias->is_contiguous() &&
-                bias->scalar_type() == torch::kBFloat16 && bias->numel() == n,
-                "decode_gemm_int4: bias must be contiguous bf16 with N elements");
-    bp = bias->const_data_ptr();
-  }
-  if (ksplit == 0) {
-    // as the int8 streamer: ~1024 workgroups, but the fp32 partials cost
-    // ksplit*M*N*8 B of traffic next to a weight stream of only K*N/2 B,
-    // so every split keeps at least kmin k rows (4-8 LDS tiles)
-    const int64_t nblk = n / 256;
-    const int64_t kmin = nblk <= 24 ? 256 : 512;
-    ksplit = std::min<int64_t>(std::max<int64_t>(1, 1024 / nblk),
-                               std::max<int64_t>(1, k / kmin));
-  }
-  const int64_t ks = pa::decode_gemm_int4_splits(k, ksplit);
-  const int64_t mt = m <= 16 ? 16 : 32;
-  auto ws = torch::empty({ks, mt, n}, x.options().dtype(torch::kFloat));
-  auto y = torch::empty({m, n}, x.options());
+  const char* op = "decode_gemm_int4";
+  const int64_t k = check_int4_weight(qw, scale, group_size, op);
+  auto c = check_decode_stream(op, x, qw, k, "qw.size(0)*2", bias, ksplit);
   pa::decode_gemm_int4(x.const_data_ptr(), qw.const_data_ptr(),
-                       scale.const_data_ptr<float>(), bp, y.mutable_data_ptr(),
-                       ws.mutable_data_ptr<float>(), m, n, k, group_size,
-                       ksplit, cur_stream());
-  return y;
+                       scale.const_data_ptr<float>(), c.bias,
+                       c.y.mutable_data_ptr(), c.ws.mutable_data_ptr<float>(),
+                       c.m, c.n, c.k, group_size, ksplit, cur_stream());
+  return c.y;
 }
 
 Tensor dequant_int4(const Tensor& qw, const Tensor& scale, int64_t group_size,
@@ -957,34 +984,6 @@ Tensor dequant_int4(const Tensor& qw, const Tensor& scale, int64_t group_size,
                    out_dtype == torch::kBFloat16 ? pa::kBF16 : pa::kF32,
                    cur_stream());
   return out;
-}
-
-Tensor decode_gemm_mfma(const Tensor& x, const Tensor& w,
-                        const c10::optional<Tensor>& bias) {
-  CHECK_IN(x);
-  TORCH_CHECK(x.dim() == 2 && w.dim() == 2 && w.stride(1) == 1);
-  TORCH_CHECK(x.scalar_type() == torch::kBFloat16);
-  int64_t m = x.size(0), k = x.size(1), n = w.size(1);
-  TORCH_CHECK(w.size(0) == k && m <= 32 && n % 256 == 0 && k % 64 == 0);
-  // target ~1024 workgroups, but keep kchunk >= 256 (4 pipelined LDS
-  // tiles per block; kchunk == 64 degenerates to an unpipelined tile)
-  int64_t nblk = n / 256;
-  // small-N shapes need a denser grid: allow kchunk 128 to reach 2 wg/CU.
-  // Cap ksplit harder than the grid target alone suggests: the fp32
-  // partial buffer costs ksplit*M*N*8 B of write+read, which at int8
-  // weights rivals the weight stream itself (the reduce kernel measured
-  // 13% of serving kernel time at the 1024-wg target).
-  int64_t kmin = nblk <= 24 ? 256 : 512;
-  int64_t ksplit = std::min<int64_t>(std::max<int64_t>(1, 1024 / nblk),
-                                     std::max<int64_t>(1, k / kmin));
-  int64_t mt = m <= 16 ? 16 : 32;
-  auto ws = torch::empty({ksplit, mt, n}, x.options().dtype(torch::kFloat));
-  auto y = torch::empty({m, n}, x.options());
-  pa::decode_gemm_mfma(x.const_data_ptr(), w.const_data_ptr(),
-                       bias.has_value() ? bias->const_data_ptr() : nullptr,
-                       y.mutable_data_ptr(), ws.mutable_data_ptr<float>(), m,
-                       n, k, w.stride(0), ksplit, cur_stream());
-  return y;
 }
 
 // ---- MoE routing ----------------------------------------------------------

@@ -54,7 +54,7 @@ def build(verbose: bool = False) -> Path:
     OUT.mkdir(exist_ok=True)
     includes, torch_lib = _torch_paths()
     py_inc = sysconfig.get_paths()["include"]
-    deps = [CSRC / "kernels" / "api.h", CSRC / "common.h"]
+    deps = sorted(CSRC.glob("*.h")) + sorted((CSRC / "kernels").glob("*.h"))
 
     hip_sources = sorted((CSRC / "kernels").glob("*.hip"))
     objs = []

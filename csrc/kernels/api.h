@@ -268,17 +268,25 @@ void quant_fp8(const void* x, void* out, float scale, int64_t numel,
 void decode_gemm(const void* x, const void* w, const void* bias, void* y,
                  float* workspace, int64_t m, int64_t n, int64_t k,
                  int64_t ldw, int64_t ksplit, hipStream_t s);
-void decode_gemm_mfma(const void* x, const void* w, const void* bias, void* y,
-                 float* workspace, int64_t m, int64_t n, int64_t k,
-                 int64_t ldw, int64_t ksplit, hipStream_t s,
-                 const float* chscale = nullptr, bool int8w = false);
 
-// weight-only int4 decode (decode_gemm_int4.hip).  qw int8 [K/2, N]: byte
-// (kp, n) = code[2kp, n] in the low nibble, code[2kp+1, n] in the high one,
-// codes -7..7; scale fp32 [N] (group_size -1) or [K/gs, N] (gs 64 | 128);
-// w ~ code * scale / 7.  M <= 32, N % 256 == 0, K % 64 == 0, K % gs == 0.
-// `workspace` holds [decode_gemm_int4_splits(k, ksplit), padded_m, N] fp32.
-int64_t decode_gemm_int4_splits(int64_t k, int64_t ksplit);
+// MFMA W-streaming decode GEMMs (decode_gemm.hip) for three weight formats.  1 <= M <= 32, N % 256 == 0, K % 64 == 0, K <= 2^24;
+// x bf16 [M, K] contiguous; x and weight base pointers 16-byte aligned.
+// ksplit 0 = heuristic.  `workspace` holds [decode_split_plan(k, n,
+// ksplit).splits, padded_m, N] fp32 with padded_m = 16 (M <= 16) or 32.
+struct DecodeSplitPlan { int kchunk, splits; };
+DecodeSplitPlan decode_split_plan(int64_t k, int64_t n, int64_t ksplit);
+// w bf16 [K, N] with row stride ldw, ldw % 8 == 0
+void decode_gemm_mfma(const void* x, const void* w, const void* bias, void* y,
+                      float* workspace, int64_t m, int64_t n, int64_t k,
+                      int64_t ldw, int64_t ksplit, hipStream_t s);
+// qw int8 [K, N] contiguous, scale fp32 [N]; w ~ code * scale / 127
+void decode_gemm_int8(const void* x, const void* qw, const float* scale,
+                      const void* bias, void* y, float* workspace, int64_t m,
+                      int64_t n, int64_t k, int64_t ksplit, hipStream_t s);
+// qw int8 [K/2, N] contiguous: byte (kp, n) = code[2kp, n] in the low
+// nibble, code[2kp+1, n] in the high one, codes -7..7; scale fp32 [N]
+// (group_size -1) or [K/gs, N] (gs 64 | 128), K % gs == 0;
+// w ~ code * scale / 7
 void decode_gemm_int4(const void* x, const void* qw, const float* scale,
                       const void* bias, void* y, float* workspace, int64_t m,
                       int64_t n, int64_t k, int64_t group_size, int64_t ksplit,

@@ -69,6 +69,40 @@ def _norm_native_ok(x, w, b=None, residual=None):
     return _kernel_ok(x, last_mult=8, same=(residual,), vecs=(w, b))
 
 
+def _decode_stream_ok(x, w, k, bias=None):
+    """Contract the MFMA decode W-streamers share (docs/KERNELS.md; pure:
+    dtypes, shapes, strides, storage offsets -- no CUDA call).  x: bf16
+    [..., K] with 1 <= rows <= 32; w: the 2-D weight tensor whose columns
+    are N, on x's device; K % 64 == 0, K <= 2^24, N % 256 == 0; x (as the
+    contiguous [rows, K] the dispatch site passes) and w start 16-byte
+    aligned; bias floating point with N elements (the site casts it)."""
+    if not (isinstance(x, torch.Tensor) and isinstance(w, torch.Tensor)
+            and x.dtype == torch.bfloat16 and x.dim() >= 1 and w.dim() == 2
+            and w.device == x.device):
+        return False
+    n = w.shape[1]
+    if k <= 0 or k % 64 or k > 2 ** 24 or n <= 0 or n % 256:
+        return False
+    if x.shape[-1] != k or not 1 <= x.numel() // k <= 32:
+        return False
+    # a non-contiguous x is copied into a fresh (aligned) allocation
+    if x.is_contiguous() and (x.storage_offset() * 2) % 16:
+        return False
+    if (w.storage_offset() * w.element_size()) % 16:
+        return False
+    return bias is None or (isinstance(bias, torch.Tensor)
+                            and bias.is_floating_point() and bias.numel() == n)
+
+
+def _decode_gemm_native_ok(x, weight, bias=None):
+    """decode_gemm_mfma: _decode_stream_ok with a bf16 [K, N] weight of unit
+    column stride and a row stride % 8 == 0 (16-byte row starts)."""
+    return (isinstance(weight, torch.Tensor) and weight.dtype == torch.bfloat16
+            and weight.dim() == 2 and weight.stride(1) == 1
+            and weight.stride(0) % 8 == 0
+            and _decode_stream_ok(x, weight, weight.shape[0], bias))
+
+
 def _bias_gelu_native_ok(x, bias=None):
     return _kernel_ok(x, last_mult=8, vecs=(bias,))
 

@@ -347,20 +347,30 @@ def _wo_int4_dequant_native_ok(qweight, scale, group_size, out_dtype):
 
 def _wo_int4_native_ok(x, qweight, scale, bias=None, group_size=-1):
     """Contract of the decode_gemm_int4 streamer (pure: dtypes, shapes,
-    contiguity -- no CUDA call): bf16 x with <= 32 rows, N % 256 == 0,
-    K % 64 == 0, group_size in (-1, 64, 128) with K % group_size == 0."""
+    contiguity, storage offsets -- no CUDA call): the shared streamer
+    contract (bf16 x with 1..32 rows, N % 256 == 0, K % 64 == 0, 16-byte
+    aligned starts) with packed int4 storage, group_size in (-1, 64, 128)
+    and K % group_size == 0."""
     import torch
-    if not (isinstance(x, torch.Tensor) and x.dtype == torch.bfloat16
-            and x.dim() >= 1 and x.numel() > 0):
-        return False
-    if not _wo_int4_dequant_native_ok(qweight, scale, group_size, x.dtype):
-        return False
-    k, n = 2 * qweight.shape[0], qweight.shape[1]
-    if x.shape[-1] != k or x.numel() // k > 32:
-        return False
-    if n % 256 or k % 64:
-        return False
-    return bias is None or (bias.is_floating_point() and bias.numel() == n)
+    from ..ops.functional import _decode_stream_ok
+    return (_wo_int4_dequant_native_ok(qweight, scale, group_size,
+                                       torch.bfloat16)
+            and _decode_stream_ok(x, qweight, 2 * qweight.shape[0], bias))
+
+
+def _wo_int8_native_ok(x, qweight, scale, bias=None):
+    """Contract of the decode_gemm_int8 streamer (pure, as above): the
+    shared streamer contract with an int8 contiguous [K, N] qweight and a
+    contiguous fp32 [N] scale on its device."""
+    import torch
+    from ..ops.functional import _decode_stream_ok
+    return (isinstance(qweight, torch.Tensor) and isinstance(scale, torch.Tensor)
+            and qweight.dtype == torch.int8 and qweight.dim() == 2
+            and qweight.is_contiguous()
+            and scale.dtype == torch.float32 and scale.is_contiguous()
+            and scale.device == qweight.device
+            and tuple(scale.shape) == (qweight.shape[1],)
+            and _decode_stream_ok(x, qweight, qweight.shape[0], bias))
 
 
 def weight_only_linear(x, qweight, scale, bias=None, weight_dtype="int8",
@@ -369,20 +379,18 @@ def weight_only_linear(x, qweight, scale, bias=None, weight_dtype="int8",
     run the int8 / int4 MFMA W-streaming kernel; int4 prefill shapes
     dequantize in one dequant_int4 pass; the fallback dequantizes in
     torch.  int4 operands use the weight_quantize storage format."""
-    import torch
     from .. import _ext
     wd = _wo_check(weight_dtype=weight_dtype, group_size=group_size)
     if wd == "int4":
         return _wo_int4_linear(x, qweight, scale, bias, group_size)
     k, n = qweight.shape
-    if x.is_cuda and _ext.use_native(x):
-        rows = x.numel() // x.shape[-1]
-        if rows <= 32 and n % 256 == 0 and k % 64 == 0 and x.dtype == torch.bfloat16:
-            C = _ext.get_ext()
-            b = bias.to(torch.bfloat16) if bias is not None else None
-            out = C.decode_gemm_int8(x.reshape(-1, k), qweight,
-                                     scale.float(), b)
-            return out.reshape(*x.shape[:-1], n)
+    if (x.is_cuda and _ext.use_native(x)
+            and _wo_int8_native_ok(x, qweight, scale, bias)):
+        C = _ext.get_ext()
+        b = bias.to(x.dtype).contiguous() if bias is not None else None
+        out = C.decode_gemm_int8(x.reshape(-1, k).contiguous(), qweight,
+                                 scale, b)
+        return out.reshape(*x.shape[:-1], n)
     w = (qweight.float() * scale.unsqueeze(0) / 127.0).to(x.dtype)  # [K,N]
     out = x @ w
     if bias is not None:
