@@ -735,6 +735,142 @@ Tensor decode_attention(const Tensor& q, const Tensor& kcache, const Tensor& vca
   return o;
 }
 
+// ---- int8 paged KV cache ---------------------------------------------------
+// Contract shared by kv_quant_append and decode_attention_int8 (docs/
+// KERNELS.md): int8 contiguous [nblocks, bs, HKV, D] code pools of equal
+// shape, D in {64, 128}; fp32 contiguous scales, both [nblocks, bs, HKV]
+// (per token) or both [HKV] (per head).  Returns true for per-token scales.
+static bool check_kv_int8_pools(const Tensor& kcache, const Tensor& vcache,
+                                const Tensor& kscale, const Tensor& vscale,
+                                const at::Device& dev, const char* op) {
+  for (const Tensor* t : {&kcache, &vcache, &kscale, &vscale})
+    TORCH_CHECK(t->is_cuda() && t->device() == dev, op,
+                ": all tensors must be on one GPU");
+  TORCH_CHECK(kcache.scalar_type() == torch::kChar &&
+              vcache.scalar_type() == torch::kChar, op, ": caches must be int8");
+  TORCH_CHECK(kcache.dim() == 4 && kcache.is_contiguous() &&
+              vcache.is_contiguous() && kcache.sizes() == vcache.sizes(), op,
+              ": caches must be contiguous [nblocks, block_size, HKV, D] of "
+              "equal shape");
+  const int64_t d = kcache.size(3);
+  TORCH_CHECK(d == 64 || d == 128, op, ": D must be 64 or 128, got ", d);
+  TORCH_CHECK(kcache.numel() > 0, op, ": empty cache");
+  TORCH_CHECK(kscale.scalar_type() == torch::kFloat &&
+              vscale.scalar_type() == torch::kFloat &&
+              kscale.is_contiguous() && vscale.is_contiguous(), op,
+              ": scales must be contiguous float32");
+  TORCH_CHECK(kscale.sizes() == vscale.sizes(), op,
+              ": k_scale and v_scale must be of the same kind");
+  const bool per_token = kscale.dim() == 3;
+  if (per_token) {
+    TORCH_CHECK(kscale.size(0) == kcache.size(0) &&
+                kscale.size(1) == kcache.size(1) &&
+                kscale.size(2) == kcache.size(2), op,
+                ": per-token scales must be [nblocks, block_size, HKV]");
+  } else {
+    TORCH_CHECK(kscale.dim() == 1 && kscale.size(0) == kcache.size(2), op,
+                ": scales must be [nblocks, block_size, HKV] or [HKV]");
+  }
+  return per_token;
+}
+
+void kv_quant_append(const Tensor& k, const Tensor& v, const Tensor& kcache,
+                     const Tensor& vcache, const Tensor& kscale,
+                     const Tensor& vscale,
+                     const Tensor& blk, const Tensor& off,
+                     const c10::optional<Tensor>& k_qscale,
+                     const c10::optional<Tensor>& v_qscale) {
+  const char* op = "kv_quant_append";
+  TORCH_CHECK(k.is_cuda(), op, ": k must be a GPU tensor");
+  const bool per_token =
+      check_kv_int8_pools(kcache, vcache, kscale, vscale, k.device(), op);
+  const int64_t bs = kcache.size(1), hkv = kcache.size(2), d = kcache.size(3);
+  for (const Tensor* t : {&k, &v}) {
+    TORCH_CHECK(t->is_cuda() && t->device() == k.device(), op,
+                ": all tensors must be on one GPU");
+    TORCH_CHECK(t->scalar_type() == torch::kBFloat16 && t->dim() == 3, op,
+                ": k/v must be bfloat16 [T, HKV, D]");
+    TORCH_CHECK(t->size(0) == k.size(0) && t->size(1) == hkv && t->size(2) == d,
+                op, ": k/v must be [T, HKV, D] matching the cache");
+    TORCH_CHECK(t->stride(2) == 1 && t->stride(0) % 8 == 0 &&
+                t->stride(1) % 8 == 0 && t->stride(0) >= 0 && t->stride(1) >= 0,
+                op, ": k/v need contiguous D and token/head strides % 8 == 0");
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(t->const_data_ptr()) % 16 == 0, op,
+                ": k/v must start 16-byte aligned");
+  }
+  const int64_t t = k.size(0);
+  for (const Tensor* i : {&blk, &off})
+    TORCH_CHECK(i->is_cuda() && i->device() == k.device() &&
+                i->scalar_type() == torch::kLong && i->dim() == 1 &&
+                i->size(0) == t && i->is_contiguous(), op,
+                ": blk/off must be contiguous int64 [T] on k's device");
+  TORCH_CHECK(k_qscale.has_value() == v_qscale.has_value(), op,
+              ": give both quant scales or neither");
+  const float *kq = nullptr, *vq = nullptr;
+  if (k_qscale.has_value()) {
+    TORCH_CHECK(!per_token, op,
+                ": fixed quant scales go with per-head [HKV] dequant scales");
+    for (const Tensor* q : {&*k_qscale, &*v_qscale})
+      TORCH_CHECK(q->is_cuda() && q->device() == k.device() &&
+                  q->scalar_type() == torch::kFloat && q->dim() == 1 &&
+                  q->size(0) == hkv && q->is_contiguous(), op,
+                  ": quant scales must be contiguous float32 [HKV]");
+    kq = k_qscale->const_data_ptr<float>();
+    vq = v_qscale->const_data_ptr<float>();
+  } else {
+    TORCH_CHECK(per_token, op,
+                ": per-head [HKV] scales need k_qscale/v_qscale");
+  }
+  pa::kv_quant_append(k.const_data_ptr(), v.const_data_ptr(),
+                      kcache.mutable_data_ptr(), vcache.mutable_data_ptr(),
+                      kscale.mutable_data_ptr<float>(),
+                      vscale.mutable_data_ptr<float>(),
+                      blk.const_data_ptr<int64_t>(),
+                      off.const_data_ptr<int64_t>(), kq, vq, t, hkv, d, bs,
+                      kcache.size(0), k.stride(0), k.stride(1), v.stride(0),
+                      v.stride(1), cur_stream());
+}
+
+Tensor decode_attention_int8(const Tensor& q, const Tensor& kcache,
+                             const Tensor& vcache, const Tensor& kscale,
+                             const Tensor& vscale, const Tensor& block_table,
+                             const Tensor& seq_lens, double scale) {
+  const char* op = "decode_attention_int8";
+  TORCH_CHECK(q.is_cuda(), op, ": q must be a GPU tensor");
+  const bool per_token =
+      check_kv_int8_pools(kcache, vcache, kscale, vscale, q.device(), op);
+  TORCH_CHECK(q.scalar_type() == torch::kBFloat16 && q.dim() == 3 &&
+              q.is_contiguous(), op, ": q must be contiguous bfloat16 [B, H, D]");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(q.const_data_ptr()) % 16 == 0, op,
+              ": q must start 16-byte aligned");
+  const int64_t b = q.size(0), h = q.size(1), d = q.size(2);
+  const int64_t nblocks = kcache.size(0), bs = kcache.size(1),
+                hkv = kcache.size(2);
+  TORCH_CHECK(kcache.size(3) == d, op, ": cache D ", kcache.size(3),
+              " != q D ", d);
+  TORCH_CHECK(h > 0 && h % hkv == 0, op, ": H % HKV != 0 (", h, ", ", hkv, ")");
+  TORCH_CHECK(block_table.is_cuda() && block_table.device() == q.device() &&
+              block_table.scalar_type() == torch::kInt &&
+              block_table.dim() == 2 && block_table.size(0) == b &&
+              block_table.is_contiguous(), op,
+              ": block_table must be contiguous int32 [B, max_blocks]");
+  TORCH_CHECK(seq_lens.is_cuda() && seq_lens.device() == q.device() &&
+              seq_lens.scalar_type() == torch::kInt && seq_lens.dim() == 1 &&
+              seq_lens.size(0) == b && seq_lens.is_contiguous(), op,
+              ": seq_lens must be contiguous int32 [B]");
+  TORCH_CHECK(nblocks < (1LL << 31) && b * h < (1LL << 31) &&
+              block_table.size(1) * bs < (1LL << 31), op, ": size overflow");
+  auto o = torch::empty_like(q);
+  pa::decode_attention_int8(
+      q.const_data_ptr(), kcache.const_data_ptr(), vcache.const_data_ptr(),
+      kscale.const_data_ptr<float>(), vscale.const_data_ptr<float>(),
+      block_table.const_data_ptr<int>(), seq_lens.const_data_ptr<int>(),
+      o.mutable_data_ptr(), b, h, hkv, bs, block_table.size(1), nblocks, d,
+      (float)scale, per_token ? bs * hkv : 0, per_token ? hkv : 0, 1,
+      cur_stream());
+  return o;
+}
+
 // ---- hand-written GEMM ----------------------------------------------------
 Tensor gemm_bf16(const Tensor& a, const Tensor& b, bool b_is_nt) {
   TORCH_CHECK(a.is_cuda() && a.scalar_type() == torch::kBFloat16);
@@ -1190,6 +1326,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("vcache"), py::arg("block_table"), py::arg("seq_lens"),
         py::arg("scale"), py::arg("blk_str") = 0, py::arg("pos_str") = 0,
         py::arg("head_str") = 0, py::arg("bs_override") = 0);
+  m.def("kv_quant_append", &kv_quant_append, py::arg("k"), py::arg("v"),
+        py::arg("kcache"), py::arg("vcache"), py::arg("kscale"),
+        py::arg("vscale"), py::arg("blk"), py::arg("off"),
+        py::arg("k_qscale") = c10::nullopt, py::arg("v_qscale") = c10::nullopt);
+  m.def("decode_attention_int8", &decode_attention_int8, py::arg("q"),
+        py::arg("kcache"), py::arg("vcache"), py::arg("kscale"),
+        py::arg("vscale"), py::arg("block_table"), py::arg("seq_lens"),
+        py::arg("scale"));
   m.def("mfma_probe", &mfma_probe);
   m.def("mfma_probe32", &mfma_probe32);
   m.attr("compiled_arch") = "gfx950";

@@ -187,6 +187,30 @@ void decode_attention(const void* q, const void* kcache, const void* vcache,
                       int64_t blk_str, int64_t pos_str, int64_t head_str,
                       hipStream_t s);
 
+// ---- int8 paged KV cache ---------------------------------------------------
+// codes int8 [nblocks, bs, HKV, D]; scales fp32 addressed (blk, pos, head)
+// by element strides: per token [nblocks, bs, HKV] -> (bs*HKV, HKV, 1), per
+// head [HKV] -> (0, 0, 1).
+// kv_quant_append: k/v bf16 [T, HKV, D] by token/head strides in elements
+// (D contiguous, 16-byte aligned rows).  k_qscale/v_qscale null: per-token
+// mode, writes d = absmax * fp32(1/127) into kscale/vscale; else fixed mode,
+// code = rint(x * qscale[h]) and the scale pools are not touched.
+void kv_quant_append(const void* k, const void* v, void* kcache, void* vcache,
+                     float* kscale, float* vscale, const int64_t* blk,
+                     const int64_t* off, const float* k_qscale,
+                     const float* v_qscale, int64_t t, int64_t hkv, int64_t dh,
+                     int64_t bs, int64_t nblocks, int64_t k_tstr,
+                     int64_t k_hstr, int64_t v_tstr, int64_t v_hstr,
+                     hipStream_t s);
+void decode_attention_int8(const void* q, const void* kcache,
+                           const void* vcache, const float* kscale,
+                           const float* vscale, const int* block_table,
+                           const int* seq_lens, void* o, int64_t b, int64_t h,
+                           int64_t hkv, int64_t bs, int64_t max_blocks,
+                           int64_t nblocks, int64_t dh, float scale,
+                           int64_t ss_blk, int64_t ss_pos, int64_t ss_head,
+                           hipStream_t s);
+
 // ---- hand-written bf16 MFMA GEMM (C[m][n] = op(A) x op(B)) ----------------
 // b_is_nt: B passed as Bt[n][k] row-major (fast path); else B[k][n].
 void gemm_bf16_8p(const void* a, const void* b, void* c, int64_t m, int64_t n,

@@ -279,13 +279,46 @@ def block_multihead_attention(qkv, key_cache, value_cache, seq_lens_encoder,
     Parity: paddle/phi/kernels/fusion/gpu/block_multi_head_attention_kernel.cu
     (block_attn.h).  qkv: packed [total_tokens, 3*H*D]; key/value_cache
     [nblocks, block_size, HKV, D]; block_tables [B, max_blocks].
-    Quant / pre-cache args are unsupported.  Returns
-    (fmha_out [total, H*D], qkv, key_cache, value_cache).
+    Returns (fmha_out [total, H*D], qkv, key_cache, value_cache).
+
+    Static int8 cache: with int8 key_cache / value_cache and fp32 [HKV]
+    cache_k_quant_scales, cache_v_quant_scales, cache_k_dequant_scales,
+    cache_v_dequant_scales, the cache write stores
+    code = clamp(rint(x * quant_scale[h]), +-127) and decode attention reads
+    x^ = code * dequant_scale[h] (the per-head mode of
+    ops.functional.kv_cache_quant_append / paged_decode_attention).  Storage
+    is this project's [nblocks, block_size, HKV, D] layout with signed int8
+    codes, not the reference's uint8 + 128.  Prefill attention uses the
+    fresh (unquantised) k/v.  use_dynamic_cachekv_quant (the reference's
+    per-sequence scales) and pre-cache args are unsupported.
     """
     import torch as _t
+    from ....ops import functional as hot
     from ....ops.functional import flash_attn_varlen_func
-    if cache_k_quant_scales is not None or pre_key_cache is not None:
-        raise NotImplementedError("block_multihead_attention: quant/pre-cache unsupported")
+    if pre_key_cache is not None or pre_value_cache is not None:
+        raise NotImplementedError("block_multihead_attention: pre-cache unsupported")
+    if use_dynamic_cachekv_quant:
+        raise NotImplementedError(
+            "block_multihead_attention: use_dynamic_cachekv_quant (per-sequence "
+            "scales) is unsupported; the supported dynamic alternative is the "
+            "per-token mode of paddle_amd.ops.functional.kv_cache_quant_append "
+            "+ paged_decode_attention(k_scale=..., v_scale=...)")
+    kv_scales = (cache_k_quant_scales, cache_v_quant_scales,
+                 cache_k_dequant_scales, cache_v_dequant_scales)
+    int8_cache = any(s is not None for s in kv_scales)
+    if int8_cache:
+        if any(s is None for s in kv_scales):
+            raise ValueError("block_multihead_attention: the static int8 cache "
+                             "needs all four cache_{k,v}_{quant,dequant}_scales")
+        if key_cache.dtype != _t.int8 or value_cache.dtype != _t.int8:
+            raise ValueError("block_multihead_attention: cache quant scales "
+                             "need int8 key_cache / value_cache")
+        kv_scales = [s.reshape(-1).float().contiguous() for s in kv_scales]
+        if any(s.numel() != key_cache.shape[2] for s in kv_scales):
+            raise ValueError("block_multihead_attention: cache scales must be [HKV]")
+    elif key_cache.dtype == _t.int8:
+        raise ValueError("block_multihead_attention: an int8 cache needs the "
+                         "cache quant / dequant scales")
     from .... import _ext
     nblocks, bs, HKV, D = key_cache.shape
     B = seq_lens_this_time.shape[0]
@@ -305,6 +338,14 @@ def block_multihead_attention(qkv, key_cache, value_cache, seq_lens_encoder,
         offs.append(offs[-1] + int(t_))
 
     def _write_cache(bidx, start_pos, kk, vv):
+        if int8_cache:
+            pos = _t.arange(start_pos, start_pos + kk.shape[0],
+                            device=qkv.device)
+            hot.kv_cache_quant_append(
+                kk, vv, key_cache, value_cache, kv_scales[2], kv_scales[3],
+                block_tables[bidx].long()[pos // bs].contiguous(),
+                (pos % bs).contiguous(), kv_scales[0], kv_scales[1])
+            return
         for j in range(kk.shape[0]):
             pos = start_pos + j
             phys = int(block_tables[bidx, pos // bs])
@@ -336,7 +377,11 @@ def block_multihead_attention(qkv, key_cache, value_cache, seq_lens_encoder,
         lens = _t.tensor([dec[i] + 1 for i in dec_idx], dtype=_t.int32,
                          device=qkv.device)
         bt = block_tables[dec_idx].to(_t.int32).contiguous()
-        if _ext.use_native(qkv) and qkv.dtype == _t.bfloat16 and D in (64, 128):
+        if int8_cache:
+            od = hot.paged_decode_attention(
+                qd, key_cache, value_cache, bt, lens, 1.0 / math.sqrt(D),
+                k_scale=kv_scales[2], v_scale=kv_scales[3])
+        elif _ext.use_native(qkv) and qkv.dtype == _t.bfloat16 and D in (64, 128):
             C = _ext.get_ext()
             od = C.decode_attention(qd.contiguous(), key_cache, value_cache,
                                     bt, lens, 1.0 / math.sqrt(D))

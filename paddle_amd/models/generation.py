@@ -15,15 +15,30 @@ from ..ops import functional as hot
 
 
 class PagedKVCache:
-    """Per-layer paged cache: k/v [nblocks, block_size, HKV, D]."""
+    """Per-layer paged cache: k/v [nblocks, block_size, HKV, D].
+    kv_cache="int8" stores int8 codes plus per-token fp32 scales
+    k_scale/v_scale [nblocks, block_size, HKV] (docs/KERNELS.md "int8 KV
+    cache"); append quantises through hot.kv_cache_quant_append."""
 
     def __init__(self, num_layers, num_blocks, block_size, num_kv_heads, head_dim,
-                 batch, max_seq, device, dtype=torch.bfloat16):
+                 batch, max_seq, device, dtype=torch.bfloat16, kv_cache="bf16"):
+        if kv_cache not in ("bf16", "int8"):
+            raise ValueError(f"kv_cache must be 'bf16' or 'int8', got {kv_cache!r}")
         self.bs = block_size
         self.num_layers = num_layers
+        self.int8 = kv_cache == "int8"
         self.k = [torch.zeros(num_blocks, block_size, num_kv_heads, head_dim,
-                              device=device, dtype=dtype) for _ in range(num_layers)]
+                              device=device,
+                              dtype=torch.int8 if self.int8 else dtype)
+                  for _ in range(num_layers)]
         self.v = [torch.zeros_like(self.k[0]) for _ in range(num_layers)]
+        # per-layer scale pools; None for the bf16 cache so that
+        # paged_decode_attention(k_scale=cache.k_scale[li], ...) serves both
+        self.k_scale = [torch.zeros(num_blocks, block_size, num_kv_heads,
+                                    device=device, dtype=torch.float32)
+                        if self.int8 else None for _ in range(num_layers)]
+        self.v_scale = [torch.zeros_like(s) if self.int8 else None
+                        for s in self.k_scale]
         max_blocks = (max_seq + block_size - 1) // block_size
         assert num_blocks >= batch * max_blocks, "cache too small"
         # static block allocation: seq b owns blocks [b*max_blocks, ...)
@@ -39,6 +54,13 @@ class PagedKVCache:
                            device=k_new.device)               # [S]
         blks = self.block_table.long()[:, pos // self.bs]     # [B, S]
         offs = (pos % self.bs).unsqueeze(0).expand(B, S_new)  # [B, S]
+        if self.int8:
+            hot.kv_cache_quant_append(
+                k_new.reshape(B * S_new, HKV, D), v_new.reshape(B * S_new, HKV, D),
+                self.k[layer], self.v[layer], self.k_scale[layer],
+                self.v_scale[layer], blks.reshape(-1).contiguous(),
+                offs.reshape(-1).contiguous())
+            return
         self.k[layer][blks, offs] = k_new
         self.v[layer][blks, offs] = v_new
 
@@ -48,8 +70,9 @@ class PagedKVCache:
 
 @torch.no_grad()
 def generate_gpt(model, input_ids, max_new_tokens=16, cache_blocks=None,
-                 block_size=16, greedy=True):
-    """Greedy/sampled generation for GPTForPretraining with paged KV."""
+                 block_size=16, greedy=True, kv_cache="bf16"):
+    """Greedy/sampled generation for GPTForPretraining with paged KV
+    (kv_cache="int8": int8 codes + per-token scales, see PagedKVCache)."""
     model.eval()
     cfg = model.cfg
     B, S0 = input_ids.shape
@@ -59,7 +82,7 @@ def generate_gpt(model, input_ids, max_new_tokens=16, cache_blocks=None,
     max_seq = S0 + max_new_tokens
     nblocks = cache_blocks or (B * ((max_seq + block_size - 1) // block_size))
     cache = PagedKVCache(cfg.num_layers, nblocks, block_size, H, D, B, max_seq, dev,
-                         dtype=model.lm_head.weight.dtype)
+                         dtype=model.lm_head.weight.dtype, kv_cache=kv_cache)
 
     def layer_qkv(layer, x):
         b, s, _ = x.shape
@@ -99,7 +122,8 @@ def generate_gpt(model, input_ids, max_new_tokens=16, cache_blocks=None,
             cache_lens = cache.seq_lens + 1  # include the new token
             att = hot.paged_decode_attention(
                 q.reshape(B, H, D), cache.k[li], cache.v[li],
-                cache.block_table, cache_lens, scale)
+                cache.block_table, cache_lens, scale,
+                k_scale=cache.k_scale[li], v_scale=cache.v_scale[li])
             att = layer.attn.out_proj(att.reshape(B, 1, H * D))
             x = x + att
             x = x + layer.mlp(layer.ln2(x))
@@ -109,7 +133,7 @@ def generate_gpt(model, input_ids, max_new_tokens=16, cache_blocks=None,
 
 
 def generate_llama(model, input_ids, max_new_tokens=16, cache_blocks=None,
-                   block_size=16, greedy=True):
+                   block_size=16, greedy=True, kv_cache="bf16"):
     """Greedy/sampled generation for LlamaForCausalLM with a paged GQA KV
     cache: rope applied at the absolute position, K/V cached at
     num_kv_heads, paged decode attention broadcasting HKV -> H
@@ -127,7 +151,8 @@ def generate_llama(model, input_ids, max_new_tokens=16, cache_blocks=None,
     max_seq = S0 + max_new_tokens
     nblocks = cache_blocks or (B * ((max_seq + block_size - 1) // block_size))
     cache = PagedKVCache(cfg.num_layers, nblocks, block_size, HKV, D, B, max_seq,
-                         dev, dtype=model.lm_head.weight.dtype)
+                         dev, dtype=model.lm_head.weight.dtype,
+                         kv_cache=kv_cache)
 
     def layer_qkv(layer, x, pos0):
         b, s, _ = x.shape
@@ -171,7 +196,8 @@ def generate_llama(model, input_ids, max_new_tokens=16, cache_blocks=None,
             cache_lens = cache.seq_lens + 1
             att = hot.paged_decode_attention(
                 q.reshape(B, H, D), cache.k[li], cache.v[li],
-                cache.block_table, cache_lens, scale)
+                cache.block_table, cache_lens, scale,
+                k_scale=cache.k_scale[li], v_scale=cache.v_scale[li])
             x = x + layer.self_attn.o_proj(att.reshape(B, 1, H * D))
             x = x + layer.mlp(layer.post_attention_layernorm(x))
         cache.advance(1)

@@ -1099,12 +1099,162 @@ def l2_norm_squared(x):
 # ---------------------------------------------------------------------------
 # paged-KV decode attention (serving; block_multihead_attention parity)
 # ---------------------------------------------------------------------------
-def paged_decode_attention(q, k_cache, v_cache, block_table, seq_lens, scale=None):
+def _kv_int8_pools_ok(k_cache, v_cache, k_scale, v_scale):
+    """The int8 KV storage format (docs/KERNELS.md): int8 contiguous
+    [nblocks, bs, HKV, D] code pools of equal shape; fp32 contiguous scales
+    on the same device, both [nblocks, bs, HKV] (per token) or both [HKV]
+    (per head).  Any D: the kernels add D in {64, 128}."""
+    ts = (k_cache, v_cache, k_scale, v_scale)
+    if not all(isinstance(t, torch.Tensor) for t in ts):
+        return False
+    if any(t.device != k_cache.device for t in ts):
+        return False
+    if not (k_cache.dtype == torch.int8 and v_cache.dtype == torch.int8
+            and k_cache.dim() == 4 and k_cache.shape == v_cache.shape
+            and k_cache.is_contiguous() and v_cache.is_contiguous()
+            and k_cache.numel() > 0):
+        return False
+    if not (k_scale.dtype == torch.float32 and v_scale.dtype == torch.float32
+            and k_scale.shape == v_scale.shape
+            and k_scale.is_contiguous() and v_scale.is_contiguous()):
+        return False
+    return (tuple(k_scale.shape) == tuple(k_cache.shape[:3])
+            or tuple(k_scale.shape) == (k_cache.shape[2],))
+
+
+def _kv_int8_native_ok(q, k_cache, v_cache, k_scale, v_scale, block_table,
+                       seq_lens):
+    """Contract of decode_attention_int8 (pure: dtypes, shapes, strides,
+    devices).  q bf16 [B, H, D] (the dispatch site passes it contiguous),
+    D in {64, 128} equal to the cache's, H % HKV == 0; pools per
+    _kv_int8_pools_ok; block_table [B, max_blocks] and seq_lens [B]
+    integer tensors (the site casts them to int32)."""
+    if not (isinstance(q, torch.Tensor) and q.dtype == torch.bfloat16
+            and q.dim() == 3 and _kv_int8_pools_ok(k_cache, v_cache, k_scale,
+                                                   v_scale)):
+        return False
+    b, h, d = q.shape
+    if d not in (64, 128) or d != k_cache.shape[3] or h == 0 \
+            or h % k_cache.shape[2]:
+        return False
+    if q.is_contiguous() and (q.storage_offset() * 2) % 16:
+        return False
+    ints = (torch.int32, torch.int64)
+    if not (isinstance(block_table, torch.Tensor) and block_table.dim() == 2
+            and block_table.shape[0] == b and block_table.dtype in ints
+            and isinstance(seq_lens, torch.Tensor) and seq_lens.dim() == 1
+            and seq_lens.shape[0] == b and seq_lens.dtype in ints):
+        return False
+    return all(t.device == q.device
+               for t in (k_cache, block_table, seq_lens))
+
+
+def _kv_quant_append_native_ok(k, v, k_cache, v_cache, k_scale, v_scale, blk,
+                               off, k_quant_scale=None, v_quant_scale=None):
+    """Contract of kv_quant_append (pure).  k/v bf16 [T, HKV, D] views with
+    contiguous D, token/head strides % 8 == 0 and a 16-byte-aligned start;
+    pools per _kv_int8_pools_ok; blk/off int64 contiguous [T]; quant scales
+    both None (per-token pools) or both fp32 contiguous [HKV] (per-head
+    pools)."""
+    if not _kv_int8_pools_ok(k_cache, v_cache, k_scale, v_scale):
+        return False
+    _, _, hkv, d = k_cache.shape
+    if d not in (64, 128):
+        return False
+    for t in (k, v):
+        if not (isinstance(t, torch.Tensor) and t.dtype == torch.bfloat16
+                and t.dim() == 3 and t.device == k_cache.device
+                and tuple(t.shape) == (k.shape[0], hkv, d)
+                and t.stride(2) == 1 and t.stride(0) % 8 == 0
+                and t.stride(1) % 8 == 0 and (t.storage_offset() * 2) % 16 == 0):
+            return False
+    for i in (blk, off):
+        if not (isinstance(i, torch.Tensor) and i.dtype == torch.int64
+                and tuple(i.shape) == (k.shape[0],) and i.is_contiguous()
+                and i.device == k_cache.device):
+            return False
+    per_token = k_scale.dim() == 3
+    if (k_quant_scale is None) != (v_quant_scale is None):
+        return False
+    if k_quant_scale is None:
+        return per_token
+    return (not per_token) and all(
+        isinstance(s, torch.Tensor) and s.dtype == torch.float32
+        and tuple(s.shape) == (hkv,) and s.is_contiguous()
+        and s.device == k_cache.device
+        for s in (k_quant_scale, v_quant_scale))
+
+
+def kv_cache_quant_append(k, v, k_cache, v_cache, k_scale, v_scale, blk, off,
+                          k_quant_scale=None, v_quant_scale=None):
+    """Quantise k/v rows [T, HKV, D] to int8 and write them into the paged
+    code pools at (blk[t], off[t]) (in place; docs/KERNELS.md "int8 KV
+    cache").  Per-token mode (quant scales None; k_scale/v_scale
+    [nblocks, bs, HKV]): d = absmax(row) * fp32(1/127) is stored and
+    code = clamp(rint(x / d), +-127); a zero row stores d = 0, codes 0.
+    Per-head mode (quant scales [HKV]; k_scale/v_scale [HKV] hold the
+    caller's dequant steps and are not written):
+    code = clamp(rint(x * quant_scale[h]), +-127).
+    The torch path below defines the format."""
+    if k.shape[0] == 0:
+        return
+    if _ext.use_native(k_cache) and _kv_quant_append_native_ok(
+            k, v, k_cache, v_cache, k_scale, v_scale, blk, off,
+            k_quant_scale, v_quant_scale):
+        _ext.get_ext().kv_quant_append(k, v, k_cache, v_cache, k_scale,
+                                       v_scale, blk, off, k_quant_scale,
+                                       v_quant_scale)
+        return
+    blk, off = blk.long(), off.long()
+    for x, cache, sc, qs in ((k, k_cache, k_scale, k_quant_scale),
+                             (v, v_cache, v_scale, v_quant_scale)):
+        xf = x.float()
+        if qs is None:
+            d = xf.abs().amax(-1) * torch.tensor(1.0 / 127.0, dtype=torch.float32,
+                                                 device=x.device)
+            y = xf / d.unsqueeze(-1).masked_fill(d.unsqueeze(-1) == 0, 1.0)
+            sc[blk, off] = d
+        else:
+            y = xf * qs.float().reshape(1, -1, 1)
+        cache[blk, off] = torch.round(y).clamp_(-127, 127).to(torch.int8)
+
+
+def _kv_int8_dequant_rows(cache, sc, blocks, S):
+    """Gathered rows [S, HKV, D] of an int8 pool as fp32 x^ = code * scale."""
+    hkv, d = cache.shape[2], cache.shape[3]
+    x = cache[blocks].reshape(-1, hkv, d)[:S].float()
+    if sc.dim() == 3:
+        return x * sc[blocks].reshape(-1, hkv)[:S].unsqueeze(-1)
+    return x * sc.reshape(1, hkv, 1)
+
+
+def paged_decode_attention(q, k_cache, v_cache, block_table, seq_lens, scale=None,
+                           k_scale=None, v_scale=None):
     """One decode step. q: [B, H, D]; k/v_cache: [nblocks, block_size, HKV, D];
-    block_table: int32 [B, max_blocks]; seq_lens: int32 [B]."""
+    block_table: int32 [B, max_blocks]; seq_lens: int32 [B].
+    With k_scale/v_scale the caches are int8 code pools (docs/KERNELS.md
+    "int8 KV cache"): fp32 scales [nblocks, block_size, HKV] (per token, as
+    kv_cache_quant_append writes them) or [HKV] (per head)."""
     if scale is None:
         scale = 1.0 / math.sqrt(q.shape[-1])
-    if _ext.use_native(q) and q.dtype == torch.bfloat16 and q.shape[-1] in (64, 128):
+    int8 = k_scale is not None or v_scale is not None
+    if int8:
+        if k_scale is None or v_scale is None:
+            raise ValueError("paged_decode_attention: give both k_scale and "
+                             "v_scale or neither")
+        if not _kv_int8_pools_ok(k_cache, v_cache, k_scale, v_scale):
+            raise ValueError(
+                "paged_decode_attention: k_scale/v_scale need int8 contiguous "
+                "[nblocks, bs, HKV, D] caches of equal shape and fp32 "
+                "contiguous scales [nblocks, bs, HKV] or [HKV]")
+        if _ext.use_native(q) and _kv_int8_native_ok(
+                q, k_cache, v_cache, k_scale, v_scale, block_table, seq_lens):
+            C = _ext.get_ext()
+            return C.decode_attention_int8(
+                q.contiguous(), k_cache, v_cache, k_scale, v_scale,
+                block_table.int().contiguous(), seq_lens.int().contiguous(),
+                scale)
+    elif _ext.use_native(q) and q.dtype == torch.bfloat16 and q.shape[-1] in (64, 128):
         C = _ext.get_ext()
         return C.decode_attention(q.contiguous(), k_cache.contiguous(),
                                   v_cache.contiguous(), block_table.int().contiguous(),
@@ -1119,8 +1269,12 @@ def paged_decode_attention(q, k_cache, v_cache, block_table, seq_lens, scale=Non
         S = int(seq_lens[b])
         nb = (S + bs - 1) // bs
         blocks = block_table[b, :nb].long()
-        k = k_cache[blocks].reshape(-1, HKV, D)[:S]  # [S, HKV, D]
-        v = v_cache[blocks].reshape(-1, HKV, D)[:S]
+        if int8:
+            k = _kv_int8_dequant_rows(k_cache, k_scale, blocks, S)
+            v = _kv_int8_dequant_rows(v_cache, v_scale, blocks, S)
+        else:
+            k = k_cache[blocks].reshape(-1, HKV, D)[:S]  # [S, HKV, D]
+            v = v_cache[blocks].reshape(-1, HKV, D)[:S]
         kf = k.float().repeat_interleave(rep, dim=1)   # [S, H, D]
         vf = v.float().repeat_interleave(rep, dim=1)
         s = torch.einsum("hd,shd->hs", q[b].float(), kf) * scale

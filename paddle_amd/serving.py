@@ -237,11 +237,17 @@ class GPTModelRunner:
 
     def __init__(self, model, num_blocks=1024, block_size=16,
                  device=None, dtype=None, max_seq=2048, use_graphs=True,
-                 weight_only=False, weight_only_group_size=-1):
+                 weight_only=False, weight_only_group_size=-1,
+                 kv_cache="bf16"):
         import math
         from .ops import functional as hot
         self.hot = hot
         self.model = model.eval()
+        # kv_cache="int8": int8 code pools + per-token fp32 scale pools
+        # (about half the KV bytes; docs/KERNELS.md "int8 KV cache")
+        if kv_cache not in ("bf16", "int8"):
+            raise ValueError(f"kv_cache must be 'bf16' or 'int8', got {kv_cache!r}")
+        self.kv_int8 = kv_cache == "int8"
         if weight_only:
             # weight-only decode: True | "int8" (~2x less weight memory) or
             # "int4" (~4x less, weight_only_group_size -1 | 64 | 128);
@@ -267,9 +273,17 @@ class GPTModelRunner:
         # into it so every captured bucket replays with fixed shapes
         self.scratch_blk = num_blocks
         self.k = [torch.zeros(num_blocks + 1, block_size, self.HKV, self.D,
-                              device=dev, dtype=dt)
+                              device=dev,
+                              dtype=torch.int8 if self.kv_int8 else dt)
                   for _ in range(cfg.num_layers)]
         self.v = [torch.zeros_like(self.k[0]) for _ in range(cfg.num_layers)]
+        # the scratch block has scale rows too; None for the bf16 cache
+        self.k_scale = [torch.zeros(num_blocks + 1, block_size, self.HKV,
+                                    device=dev, dtype=torch.float32)
+                        if self.kv_int8 else None
+                        for _ in range(cfg.num_layers)]
+        self.v_scale = [torch.zeros_like(s) if self.kv_int8 else None
+                        for s in self.k_scale]
         self.seq_len = {}            # rid -> tokens currently cached
         self.last_token = {}         # rid -> next input token
         self.max_blk = (max_seq + block_size - 1) // block_size
@@ -280,6 +294,17 @@ class GPTModelRunner:
                      self.D in (64, 128) and _ext.has_ext())
         self.use_graphs = use_graphs and native_ok
         self._graphs = {}            # bucket B -> (graph, static tensors)
+
+    def _kv_write(self, li, blk, off, k, v):
+        """Store k/v rows [..., HKV, D] at (blk, off) [...] of layer li."""
+        if not self.kv_int8:
+            self.k[li][blk, off] = k
+            self.v[li][blk, off] = v
+            return
+        self.hot.kv_cache_quant_append(
+            k.reshape(-1, self.HKV, self.D), v.reshape(-1, self.HKV, self.D),
+            self.k[li], self.v[li], self.k_scale[li], self.v_scale[li],
+            blk.reshape(-1).contiguous(), off.reshape(-1).contiguous())
 
     def _qkv(self, layer, x):
         b, s, _ = x.shape
@@ -304,8 +329,7 @@ class GPTModelRunner:
         for li, layer in enumerate(m.gpt.layers):
             h = layer.ln1(x)
             q, k, v = self._qkv(layer, h)
-            self.k[li][blks, offs] = k
-            self.v[li][blks, offs] = v
+            self._kv_write(li, blks, offs, k, v)
             att, _ = self.hot.flash_attention(q, k, v, causal=True)
             x = x + layer.attn.out_proj(att.reshape(N, S0, -1))
             x = x + layer.mlp(layer.ln2(x))
@@ -413,11 +437,11 @@ class GPTModelRunner:
         for li, layer in enumerate(m.gpt.layers):
             h = layer.ln1(x)
             q, k, v = self._qkv(layer, h)
-            self.k[li][write_blk, write_off] = k[:, 0]
-            self.v[li][write_blk, write_off] = v[:, 0]
+            self._kv_write(li, write_blk, write_off, k[:, 0], v[:, 0])
             att = self.hot.paged_decode_attention(
                 q.reshape(B, self.H, self.D), self.k[li], self.v[li],
-                table, lens + 1, self.scale)
+                table, lens + 1, self.scale,
+                k_scale=self.k_scale[li], v_scale=self.v_scale[li])
             x = x + layer.attn.out_proj(att.reshape(B, 1, -1))
             x = x + layer.mlp(layer.ln2(x))
         return m.lm_head(m.gpt.final_norm(x[:, 0]))
@@ -554,8 +578,7 @@ class LlamaModelRunner(GPTModelRunner):
         for li, layer in enumerate(m.llama.layers):
             h = layer.input_layernorm(x)
             q, k, v = self._qkv(layer, h)
-            self.k[li][blks, offs] = k
-            self.v[li][blks, offs] = v
+            self._kv_write(li, blks, offs, k, v)
             att, _ = self.hot.flash_attention(q, k, v, causal=True)
             x = x + layer.self_attn.o_proj(att.reshape(N, S0, -1))
             x = x + layer.mlp(layer.post_attention_layernorm(x))
@@ -591,11 +614,11 @@ class LlamaModelRunner(GPTModelRunner):
             v = qkv[:, qo + ko:].reshape(B, 1, self.HKV, self.D)
             q = self._rope_rows(q, a_pos)
             k = self._rope_rows(k, a_pos)
-            self.k[li][write_blk, write_off] = k[:, 0]
-            self.v[li][write_blk, write_off] = v[:, 0]
+            self._kv_write(li, write_blk, write_off, k[:, 0], v[:, 0])
             att = self.hot.paged_decode_attention(
                 q.reshape(B, self.H, self.D), self.k[li], self.v[li],
-                table, lens + 1, self.scale)
+                table, lens + 1, self.scale,
+                k_scale=self.k_scale[li], v_scale=self.v_scale[li])
             x = x + layer.self_attn.o_proj(att.reshape(B, 1, -1))
             x = x + layer.mlp(layer.post_attention_layernorm(x))
         return m.lm_head(m.llama.norm(x[:, 0]))

@@ -19,13 +19,18 @@ from paddle_amd.serving import Engine, GPTModelRunner, Request  # noqa: E402
 
 def run_one(tag, model, n_req=64, prompt_len=128, gen_len=128, max_batch=32,
             num_blocks=4096, weight_only=False, runner_cls="gpt",
-            group_size=-1):
+            group_size=-1, kv_cache="bf16"):
     cls = GPTModelRunner
     if runner_cls == "llama":
         from paddle_amd.serving import LlamaModelRunner
         cls = LlamaModelRunner
     runner = cls(model, num_blocks=num_blocks, block_size=16,
-                 weight_only=weight_only, weight_only_group_size=group_size)
+                 max_seq=max(2048, prompt_len + gen_len),
+                 weight_only=weight_only, weight_only_group_size=group_size,
+                 kv_cache=kv_cache)
+    pools = runner.k + runner.v + [s for s in runner.k_scale + runner.v_scale
+                                   if s is not None]
+    pool_gb = sum(t.numel() * t.element_size() for t in pools) / 2**30
     runner.precapture((max_batch,))    # decode graph capture out of ttft
     eng = Engine(runner, num_blocks=num_blocks, block_size=16,
                  max_batch=max_batch)
@@ -57,6 +62,7 @@ def run_one(tag, model, n_req=64, prompt_len=128, gen_len=128, max_batch=32,
           f"  steady-decode {dec_toks / dt_dec:.0f} tok/s"
           f" ({dt_dec / max(n_steps,1) * 1e3:.2f} ms/step)"
           f"  ttft {s['mean_ttft_s'] * 1e3:.0f} ms"
+          f"  kv pools {pool_gb:.2f} GB"
           f"  peak {torch.cuda.max_memory_allocated() / 2**30:.1f} GB")
 
 
@@ -72,27 +78,38 @@ def main():
                     default=None, help="implies --weight-only")
     ap.add_argument("--group-size", type=int, default=-1,
                     choices=[-1, 64, 128], help="int4 scale group size")
+    ap.add_argument("--kv-cache", choices=["bf16", "int8"], default="bf16",
+                    help="paged KV pool format (int8: codes + per-token scales)")
+    ap.add_argument("--prompt-len", type=int, default=128)
+    ap.add_argument("--gen-len", type=int, default=128)
+    ap.add_argument("--n-req", type=int, default=64)
     args = ap.parse_args()
     paddle.seed(0)
     wo = args.weight_only_dtype or ("int8" if args.weight_only else False)
     tag_sfx = ""
     if wo:
         tag_sfx = f" {wo}-wo" + (f"-gs{args.group_size}" if args.group_size > 0 else "")
-    kw = dict(weight_only=wo, group_size=args.group_size)
+    if args.kv_cache != "bf16":
+        tag_sfx += f" {args.kv_cache}-kv"
+    kw = dict(weight_only=wo, group_size=args.group_size,
+              kv_cache=args.kv_cache, prompt_len=args.prompt_len,
+              gen_len=args.gen_len, n_req=args.n_req)
+    seq = max(2048, args.prompt_len + args.gen_len)
+    # blocks for max_batch sequences of prompt+gen tokens, with headroom
+    nblk = max(8192, 2 * 32 * (-(-seq // 16)))
     if args.model == "gpt-350m":
         cfg = GPTConfig(vocab_size=50304, hidden_size=1024, num_layers=24,
-                        num_heads=16, intermediate_size=4096, max_seq_len=2048)
+                        num_heads=16, intermediate_size=4096, max_seq_len=seq)
         m = GPTForPretraining(cfg).to("cuda", torch.bfloat16)
         run_one("gpt-350M" + tag_sfx, m, **kw)
     elif args.model == "gpt3-6.7b":
-        m = build_gpt("gpt3-6.7b", max_seq_len=2048).to("cuda", torch.bfloat16)
-        run_one("gpt3-6.7B" + tag_sfx, m, n_req=64, max_batch=32,
-                num_blocks=8192, **kw)
+        m = build_gpt("gpt3-6.7b", max_seq_len=seq).to("cuda", torch.bfloat16)
+        run_one("gpt3-6.7B" + tag_sfx, m, max_batch=32, num_blocks=nblk, **kw)
     else:
         from paddle_amd.models.llama import build_llama
-        m = build_llama("llama2-7b", max_seq_len=2048).to("cuda", torch.bfloat16)
-        run_one("llama2-7B" + tag_sfx, m, n_req=64, max_batch=32,
-                num_blocks=8192, runner_cls="llama", **kw)
+        m = build_llama("llama2-7b", max_seq_len=seq).to("cuda", torch.bfloat16)
+        run_one("llama2-7B" + tag_sfx, m, max_batch=32, num_blocks=nblk,
+                runner_cls="llama", **kw)
 
 
 if __name__ == "__main__":
