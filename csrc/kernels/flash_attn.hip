@@ -5,10 +5,14 @@
 // MI355X-first design (NOT a port of the reference's dynloaded
 // libflashattn -- paddle/phi/kernels/gpu/flash_attn_kernel.cu:41 is a
 // dispatch shim; the math here is re-derived):
-//   * MFMA 16x16x32 bf16 tiles; 4 waves/block; each wave owns 16 rows of
-//     the 64-row Q (fwd) / KV (bwd-dkv) tile.
-//   * K / V^T staged in LDS with the XOR-16B swizzle (guide §6 G4) so
-//     column-sliced ds_read_b128 is ~2-way conflict free.
+//   * MFMA 16x16x32 bf16 tiles; 8 waves/block; each wave owns 16 rows of
+//     the 128-row Q (fwd, bwd-dq) / KV (bwd-dkv) block.
+//   * fwd / bwd-dq: K / V^T staged in LDS with the XOR-16B swizzle (guide
+//     §6 G4) so column-sliced ds_read_b128 is ~2-way conflict free, the
+//     transposed tile written as a second copy.
+//   * bwd-dkv: Q / dO staged once per tile by DMA into one image that is
+//     read by rows (ds_read_b128) and by columns (ds_read_b64_tr_b16), two
+//     buffers so the next tile loads under this tile's math (see the kernel).
 //   * online softmax entirely in registers; row stats shared across the
 //     16-lane C-tile groups via shfl_xor(1,2,4,8).
 //   * LSE saved (fp32) for backward + ring/context-parallel merges.
@@ -346,9 +350,130 @@ void flash_attn_bwd_delta(const void* dout, const void* o, float* delta,
 }
 
 // ---------------------------------------------------------------------------
-// backward dK/dV: block owns a 64-row KV tile; waves own 16 kv rows each;
-// iterate q tiles.  S^T computed as K·Q^T so kv is the C-row.
+// backward dK/dV: block owns a 128-row KV block; waves own 16 kv rows each;
+// iterate 64-row q tiles.  S^T computed as K·Q^T so kv is the C-row.
+//
+// Q and dO are staged once per tile, by DMA, in ONE LDS image that serves
+// both kinds of read: ds_read_b128 rows for the B operand of S^T / dP^T
+// (k = d) and ds_read_b64_tr_b16 for the B operand of dV / dK (k = q), so no
+// transposed copy is built.  The image is the natural [64][D] tile with the
+// 16-byte chunk index of each row XORed by dkv_swz(row); the DMA lands it
+// through the same XOR on its source column.  Two {Q, dO} buffers: tile t+1
+// is in flight while tile t is computed, one barrier per tile.  P^T and dS^T
+// cross a per-wave [q][kv] image as packed 8-byte rows and come back as A
+// fragments by transposed reads.  Every MFMA gets the operands, in the k
+// order, of the kernel this replaces, so dK / dV are bit-identical to it.
 // ---------------------------------------------------------------------------
+
+// chunk-index XOR of row `row` of the [64][D] image.  Bank rule: a 256-byte
+// bank row; ds_read_b64_tr_b16 conflicts inside a 32-lane half, ds_read_b128
+// inside its 16-lane groups {0-3,12-15,20-27}, {4-11,16-19,28-31} (+32).
+//   transposed read: a half takes rows 8g+4h+{0..3} of two 16-lane groups
+//     g, g+1, 32 bytes per row, the same chunk pair 2*dt, 2*dt+1 -> the 8
+//     rows must land on 8 different 32-byte pairs;
+//   row read (16x16x32 B operand): a group takes rows {0-3,12-15} at chunk c
+//     and rows {4-11} at chunk c^1 (or the other way round) -> 16 slots.
+// D = 128: pair bits from row&3 and (row>>3)&1, bit 0 clear.  Rows r and r+4
+// share a pair and differ in c's bit 0, so both reads are conflict-free (the
+// guide's T10 image (b), bits 1:0 = (row>>2)&3, is 2-way on this row read),
+// and rows +4 / +32 keep the XOR, so the second half of a B fragment and the
+// next k-step are immediate offsets from one address register per d tile.
+// D = 64 has two rows per bank row: row&1 picks the half, (row>>1)&1 and
+// (row>>3)&1 the pair inside it; the same two properties hold.
+template <int D>
+__device__ __forceinline__ unsigned dkv_swz(unsigned row) {
+  if constexpr (D == 128)
+    return ((row & 3u) << 2) | (((row >> 3) & 1u) << 1);
+  else
+    return (((row >> 1) & 1u) << 2) | (((row >> 3) & 1u) << 1);
+}
+
+// byte offset of 16-byte chunk `ch` of row `row`; stores and both kinds of
+// read go through it
+template <int D>
+__device__ __forceinline__ unsigned dkv_off(unsigned row, unsigned ch) {
+  return row * (D * 2) + ((ch ^ dkv_swz<D>(row)) << 4);
+}
+
+// ds_read_b64_tr_b16: per 16-lane group, lane 4q+p passes the address of row
+// q, columns 4p..4p+3 of a 4-row x 16-column block; lane i gets column i,
+// row j in element j.  EXEC must be all ones at every one of these.
+//
+// The transposed reads are inline asm that ends in its own lgkmcnt(0): as a
+// builtin each read was waited for on its own in front of its MFMA, and the
+// first one of a tile drew a vmcnt(0) that drained the prefetch of the next
+// tile.  One statement reads the B fragments B[k = r0 + 0..7][n = 16*dt + l16]
+// of four d tiles: a0..a3 are the LDS addresses of rows r0..r0+3 (lane's row
+// r0 + l16/4, its 8 bytes of chunk pair 2*dt), LO the byte offset added for
+// r0 inside the tile, HI that of rows r0+4..r0+7.
+template <int LO, int HI>
+__device__ __forceinline__ void dkv_tr_read4(shortx8 (&b)[4], unsigned a0, unsigned a1,
+                                             unsigned a2, unsigned a3) {
+  shortx4 l0, h0, l1, h1, l2, h2, l3, h3;
+  asm volatile(
+      "ds_read_b64_tr_b16 %0, %8 offset:%12\n\t"
+      "ds_read_b64_tr_b16 %1, %8 offset:%13\n\t"
+      "ds_read_b64_tr_b16 %2, %9 offset:%12\n\t"
+      "ds_read_b64_tr_b16 %3, %9 offset:%13\n\t"
+      "ds_read_b64_tr_b16 %4, %10 offset:%12\n\t"
+      "ds_read_b64_tr_b16 %5, %10 offset:%13\n\t"
+      "ds_read_b64_tr_b16 %6, %11 offset:%12\n\t"
+      "ds_read_b64_tr_b16 %7, %11 offset:%13\n\t"
+      "s_waitcnt lgkmcnt(0)"
+      : "=&v"(l0), "=&v"(h0), "=&v"(l1), "=&v"(h1), "=&v"(l2), "=&v"(h2), "=&v"(l3), "=&v"(h3)
+      : "v"(a0), "v"(a1), "v"(a2), "v"(a3), "n"(LO), "n"(HI)
+      : "memory");
+  b[0] = __builtin_shufflevector(l0, h0, 0, 1, 2, 3, 4, 5, 6, 7);
+  b[1] = __builtin_shufflevector(l1, h1, 0, 1, 2, 3, 4, 5, 6, 7);
+  b[2] = __builtin_shufflevector(l2, h2, 0, 1, 2, 3, 4, 5, 6, 7);
+  b[3] = __builtin_shufflevector(l3, h3, 0, 1, 2, 3, 4, 5, 6, 7);
+}
+
+// per-wave P^T / dS^T image [64 q][16 kv], 32-byte rows: byte offset of kv
+// rows 4*slot..4*slot+3 of q column `q`.  Bit 2 of the row is flipped on odd
+// 8-row groups so the two 16-lane groups of a transposed read use opposite
+// halves of the bank row; the slot XOR spreads the 16 lanes of a packed
+// 8-byte store over all 32 store banks.
+__device__ __forceinline__ unsigned dkv_p_off(unsigned q, unsigned slot) {
+  return ((q ^ ((q >> 1) & 4u)) << 5) + ((slot ^ ((q >> 2) & 3u)) << 3);
+}
+
+// both A fragments A[m = l16][k = 32*kk + 8*lg + 0..7] of the wave image,
+// after the wave's own stores to it have landed.  a_lo / a_hi: addresses of
+// the lane's row in rows 8*lg+{0..3} / 8*lg+{4..7}; k-step 1 is 32 rows on.
+__device__ __forceinline__ void dkv_tr_read_pa(shortx8 (&pa)[2], unsigned a_lo, unsigned a_hi) {
+  shortx4 l0, h0, l1, h1;
+  asm volatile(
+      "s_waitcnt lgkmcnt(0)\n\t"
+      "ds_read_b64_tr_b16 %0, %4\n\t"
+      "ds_read_b64_tr_b16 %1, %5\n\t"
+      "ds_read_b64_tr_b16 %2, %4 offset:1024\n\t"
+      "ds_read_b64_tr_b16 %3, %5 offset:1024\n\t"
+      "s_waitcnt lgkmcnt(0)"
+      : "=&v"(l0), "=&v"(h0), "=&v"(l1), "=&v"(h1)
+      : "v"(a_lo), "v"(a_hi)
+      : "memory");
+  pa[0] = __builtin_shufflevector(l0, h0, 0, 1, 2, 3, 4, 5, 6, 7);
+  pa[1] = __builtin_shufflevector(l1, h1, 0, 1, 2, 3, 4, 5, 6, 7);
+}
+
+// acc[dt] += A * B[k = r0 + 0..7][n = 16*dt + l16] over all d tiles, B by
+// transposed reads four d tiles at a time.  bt_a[dt]: the lane's address for
+// rows 0..3 of buffer 0's Q tile; OFF: byte offset of the tile and of r0 in
+// it; boff: byte offset of the buffer.
+template <int D, int OFF>
+__device__ __forceinline__ void dkv_mma_tr(floatx4* acc, shortx8 a, const unsigned* bt_a,
+                                           unsigned boff) {
+#pragma unroll
+  for (int g = 0; g < D / 64; ++g) {
+    shortx8 b[4];
+    dkv_tr_read4<OFF, OFF + 4 * D * 2>(b, boff + bt_a[4 * g], boff + bt_a[4 * g + 1],
+                                       boff + bt_a[4 * g + 2], boff + bt_a[4 * g + 3]);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) acc[4 * g + i] = mfma_bf16(a, b[i], acc[4 * g + i]);
+  }
+}
+
 template <int D, bool CAUSAL>
 __launch_bounds__(512)
 __global__ void fa_bwd_dkv_kernel(const short* __restrict__ dog, const short* __restrict__ qg,
@@ -366,13 +491,12 @@ __global__ void fa_bwd_dkv_kernel(const short* __restrict__ dog, const short* __
   constexpr int QB = 64;
   constexpr int NKK = D / 32;
   constexpr int NDT = D / 16;
-  constexpr unsigned NAT_RS = D * 2;   // natural [64][D]
-  constexpr unsigned TR_RS = QB * 2;   // transposed [D][64]
-  __shared__ char q_lds[QB * D * 2];
-  __shared__ char qt_lds[D * QB * 2];
-  __shared__ char do_lds[QB * D * 2];
-  __shared__ char dot_lds[D * QB * 2];
-  __shared__ char ps_lds[NW * 16 * QB * 2];
+  constexpr int TILE = QB * D * 2;           // bytes of one [64][D] tile
+  constexpr int NIT = QB * D / (NT * 8);     // DMA instructions per tile
+  constexpr int PW = 16 * QB * 2;            // bytes of one wave's P/dS image
+  // one array (a second __shared__ object beside a DMA target can cost a
+  // vmcnt(0) per LDS read): two {Q, dO} buffers, then the per-wave images
+  __shared__ __attribute__((aligned(16))) char lds[4 * TILE + NW * PW];
 
   const int kvblk = blockIdx.y;     // slow dim; kv0=0 (longest) first
   const int bh = blockIdx.x;
@@ -415,48 +539,33 @@ __global__ void fa_bwd_dkv_kernel(const short* __restrict__ dog, const short* __
 
   const int q_start = CAUSAL ? (kv0 / QB) * QB : 0;
 
-  // DMA staging maps for the natural [64][D] tiles (pre-swizzled source)
-  int n_row[QB * D / (NT * 8)], n_colp[QB * D / (NT * 8)];
+  // DMA staging map: lane `tid` of instruction `it` fills 16 LDS bytes at
+  // it*NT*16 + tid*16 (the DMA target is lane-linear), i.e. chunk position
+  // col/8 of row n_row; the chunk that belongs there is position ^ swz(row)
+  int n_row[NIT], n_colp[NIT];
 #pragma unroll
-  for (int it = 0; it < QB * D / (NT * 8); ++it) {
+  for (int it = 0; it < NIT; ++it) {
     int flat = it * NT * 8 + tid * 8;
     int row = flat / D, col = flat % D;
     n_row[it] = row;
-    n_colp[it] = col ^ ((row & 7) << 3);
+    n_colp[it] = col ^ (int)(dkv_swz<D>(row) << 3);
   }
 
-  for (int q0 = q_start; q0 < Sq; q0 += QB) {
-    // stage Q, dO natural (async DMA when in-bounds) + transposed (reg)
+  // stage the Q tile at q0 into qbuf and the dO tile into qbuf + TILE: DMA
+  // for a whole tile, zero-padded ordinary stores for the tail tile
+  auto stage = [&](int q0, char* qbuf) {
     if (q0 + QB <= Sq) {
 #pragma unroll
-      for (int it = 0; it < QB * D / (NT * 8); ++it) {
+      for (int it = 0; it < NIT; ++it) {
         const short* qsrc = qg + qbase + (long long)(q0 + n_row[it]) * q_ss + n_colp[it];
         const short* dsrc = dog + dobase + (long long)(q0 + n_row[it]) * do_ss + n_colp[it];
+        char* dst = qbuf + it * NT * 16 + (tid >> 6) * 64 * 16;
         __builtin_amdgcn_global_load_lds(
             (const __attribute__((address_space(1))) unsigned int*)qsrc,
-            (__attribute__((address_space(3))) unsigned int*)(q_lds + it * NT * 16 + (tid >> 6) * 64 * 16),
-            16, 0, 0);
+            (__attribute__((address_space(3))) unsigned int*)dst, 16, 0, 0);
         __builtin_amdgcn_global_load_lds(
             (const __attribute__((address_space(1))) unsigned int*)dsrc,
-            (__attribute__((address_space(3))) unsigned int*)(do_lds + it * NT * 16 + (tid >> 6) * 64 * 16),
-            16, 0, 0);
-      }
-      // transposed copies from the DMA-landed natural tiles (LDS round
-      // trip) -- re-reading Q/dO from global doubled this kernel's HBM
-      // traffic, and the kernel is Q/dO-stream-bound
-      __syncthreads();
-      constexpr int elems = QB * D;
-      const int rot = threadIdx.x & 7;
-      for (int flat = tid * 8; flat < elems; flat += NT * 8) {
-        int row = flat / D, col = flat % D;
-        shortx8 qv = lds_read8(q_lds, row, col, NAT_RS);
-        shortx8 dv = lds_read8(do_lds, row, col, NAT_RS);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          int i = (j + rot) & 7;
-          *reinterpret_cast<short*>(qt_lds + lds_off(col + i, row * 2, TR_RS)) = qv[i];
-          *reinterpret_cast<short*>(dot_lds + lds_off(col + i, row * 2, TR_RS)) = dv[i];
-        }
+            (__attribute__((address_space(3))) unsigned int*)(dst + TILE), 16, 0, 0);
       }
     } else {
       constexpr int elems = QB * D;
@@ -469,27 +578,56 @@ __global__ void fa_bwd_dkv_kernel(const short* __restrict__ dog, const short* __
         } else {
           for (int i = 0; i < 8; ++i) { qv[i] = 0; dv[i] = 0; }
         }
-        *reinterpret_cast<shortx8*>(q_lds + lds_off(row, col * 2, NAT_RS)) = qv;
-        *reinterpret_cast<shortx8*>(do_lds + lds_off(row, col * 2, NAT_RS)) = dv;
-        const int rot = threadIdx.x & 7;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          int i = (j + rot) & 7;
-          *reinterpret_cast<short*>(qt_lds + lds_off(col + i, row * 2, TR_RS)) = qv[i];
-          *reinterpret_cast<short*>(dot_lds + lds_off(col + i, row * 2, TR_RS)) = dv[i];
-        }
+        const unsigned o = dkv_off<D>(row, col >> 3);
+        *reinterpret_cast<shortx8*>(qbuf + o) = qv;
+        *reinterpret_cast<shortx8*>(qbuf + TILE + o) = dv;
       }
     }
-    __syncthreads();
-
-    // per-lane lse/delta for the 4 q-subtiles (indexed by C-col = q)
-    float lse_v[4], delta_v[4];
+  };
+  // per-lane lse/delta of the 4 q-subtiles (indexed by C-col = q)
+  auto load_stats = [&](int q0, float* lse_o, float* delta_o) {
 #pragma unroll
     for (int nt = 0; nt < 4; ++nt) {
       int q_abs = q0 + nt * 16 + l16;
-      lse_v[nt] = (q_abs < Sq) ? lseg[lse_base + q_abs] : INFINITY;
-      delta_v[nt] = (q_abs < Sq) ? deltag[lse_base + q_abs] : 0.f;
+      lse_o[nt] = (q_abs < Sq) ? lseg[lse_base + q_abs] : INFINITY;
+      delta_o[nt] = (q_abs < Sq) ? deltag[lse_base + q_abs] : 0.f;
     }
+  };
+
+  char* const pw = lds + 4 * TILE + wq * PW;
+  // LDS addresses of the lane's rows for the transposed reads
+  const unsigned lds_a = (unsigned)(size_t)(__attribute__((address_space(3))) char*)lds;
+  const unsigned tr_q = l16 >> 2, tr_p = l16 & 3;
+  unsigned bt_a[NDT];
+#pragma unroll
+  for (int dt = 0; dt < NDT; ++dt)
+    bt_a[dt] = lds_a + dkv_off<D>(8 * lg + tr_q, 2 * dt + (tr_p >> 1)) + ((tr_p & 1) << 3);
+  const unsigned pa_lo = lds_a + 4 * TILE + wq * PW + dkv_p_off(8 * lg + tr_q, tr_p);
+  const unsigned pa_hi = lds_a + 4 * TILE + wq * PW + dkv_p_off(8 * lg + 4 + tr_q, tr_p);
+  float lse_n[4], delta_n[4];
+  if (q_start < Sq) {
+    stage(q_start, lds);
+    load_stats(q_start, lse_n, delta_n);
+  }
+  int cur = 0;
+  for (int q0 = q_start; q0 < Sq; q0 += QB) {
+    // Tile q0 was issued one tile ago (or in the prologue) and nothing newer
+    // is in flight, so the counted wait is vmcnt(0).  The one barrier per
+    // tile then says both "tile q0 has landed for every wave" and "every
+    // wave is done reading tile q0-QB", which frees the other buffer.
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    const unsigned boff = cur * (2 * TILE);
+    const char* q_t = lds + boff;
+    float lse_v[4], delta_v[4];
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt) { lse_v[nt] = lse_n[nt]; delta_v[nt] = delta_n[nt]; }
+    if (q0 + QB < Sq) {
+      stage(q0 + QB, lds + (cur ^ 1) * (2 * TILE));
+      load_stats(q0 + QB, lse_n, delta_n);
+    }
+    cur ^= 1;
+    const char* do_t = q_t + TILE;
 
     // S^T = K Q^T ; P^T = exp(S^T*scale - lse[q])
     floatx4 pt[4];
@@ -499,7 +637,8 @@ __global__ void fa_bwd_dkv_kernel(const short* __restrict__ dog, const short* __
       floatx4 st = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int kk = 0; kk < NKK; ++kk) {
-        shortx8 qfr = lds_read8(q_lds, nt * 16 + l16, kk * 32 + lg * 8, NAT_RS);
+        shortx8 qfr = *reinterpret_cast<const shortx8*>(
+            q_t + dkv_off<D>(nt * 16 + l16, kk * 4 + lg));
         st = mfma_bf16(kf[kk], qfr, st);
       }
       const int q_abs = q0 + nt * 16 + l16;
@@ -520,26 +659,22 @@ __global__ void fa_bwd_dkv_kernel(const short* __restrict__ dog, const short* __
       }
     }
 
-    // write P^T to wave LDS  [kv16][q64]
-    char* pw = ps_lds + wq * (16 * QB * 2);
+    // P^T (then dS^T) to the wave's [q][kv] image: a lane holds kv rows
+    // 4*lg..4*lg+3 of q column nt*16+l16, one packed 8-byte store per C tile
+    shortx8 pa[2];
+    auto put_get = [&]() {
 #pragma unroll
-    for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-        *reinterpret_cast<short*>(pw + lds_off(lg * 4 + r, (nt * 16 + l16) * 2, QB * 2)) =
-            f2bf(pt[nt][r]);
-    LGKM0();
-
-    // dV += P^T dO   (A = P^T from LDS, B = dO^T tile)
-#pragma unroll
-    for (int kk = 0; kk < QB / 32; ++kk) {
-      shortx8 pa = lds_read8(pw, l16, kk * 32 + lg * 8, QB * 2);
-#pragma unroll
-      for (int dt = 0; dt < NDT; ++dt) {
-        shortx8 bfr = lds_read8(dot_lds, dt * 16 + l16, kk * 32 + lg * 8, TR_RS);
-        dv_acc[dt] = mfma_bf16(pa, bfr, dv_acc[dt]);
+      for (int nt = 0; nt < 4; ++nt) {
+        shortx4 v = {f2bf(pt[nt][0]), f2bf(pt[nt][1]), f2bf(pt[nt][2]), f2bf(pt[nt][3])};
+        *reinterpret_cast<shortx4*>(pw + dkv_p_off(nt * 16 + l16, lg)) = v;
       }
-    }
+      dkv_tr_read_pa(pa, pa_lo, pa_hi);
+    };
+    put_get();
+
+    // dV += P^T dO   (A = P^T from the wave image, B = dO by transposed reads)
+    dkv_mma_tr<D, TILE>(dv_acc, pa[0], bt_a, boff);
+    dkv_mma_tr<D, TILE + 32 * D * 2>(dv_acc, pa[1], bt_a, boff);
 
     // dP^T = V dO^T
 #pragma unroll
@@ -547,7 +682,8 @@ __global__ void fa_bwd_dkv_kernel(const short* __restrict__ dog, const short* __
       floatx4 dp = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int kk = 0; kk < NKK; ++kk) {
-        shortx8 bfr = lds_read8(do_lds, nt * 16 + l16, kk * 32 + lg * 8, NAT_RS);
+        shortx8 bfr = *reinterpret_cast<const shortx8*>(
+            do_t + dkv_off<D>(nt * 16 + l16, kk * 4 + lg));
         dp = mfma_bf16(vf[kk], bfr, dp);
       }
       // dS^T = P^T * (dP^T - delta[q]) * scale
@@ -555,26 +691,11 @@ __global__ void fa_bwd_dkv_kernel(const short* __restrict__ dog, const short* __
       for (int r = 0; r < 4; ++r)
         pt[nt][r] = pt[nt][r] * (dp[r] - delta_v[nt]) * scale;
     }
-    LGKM0();  // ensure dV reads of pw done before overwrite
-#pragma unroll
-    for (int nt = 0; nt < 4; ++nt)
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-        *reinterpret_cast<short*>(pw + lds_off(lg * 4 + r, (nt * 16 + l16) * 2, QB * 2)) =
-            f2bf(pt[nt][r]);
-    LGKM0();
+    put_get();   // the reads of P^T ended inside the first put_get
 
-    // dK += dS^T Q  (B = Q^T tile)
-#pragma unroll
-    for (int kk = 0; kk < QB / 32; ++kk) {
-      shortx8 pa = lds_read8(pw, l16, kk * 32 + lg * 8, QB * 2);
-#pragma unroll
-      for (int dt = 0; dt < NDT; ++dt) {
-        shortx8 bfr = lds_read8(qt_lds, dt * 16 + l16, kk * 32 + lg * 8, TR_RS);
-        dk_acc[dt] = mfma_bf16(pa, bfr, dk_acc[dt]);
-      }
-    }
-    __syncthreads();
+    // dK += dS^T Q  (B = Q by transposed reads)
+    dkv_mma_tr<D, 0>(dk_acc, pa[0], bt_a, boff);
+    dkv_mma_tr<D, 32 * D * 2>(dk_acc, pa[1], bt_a, boff);
   }
 
   // write dK, dV
