@@ -871,6 +871,94 @@ Tensor decode_attention_int8(const Tensor& q, const Tensor& kcache,
   return o;
 }
 
+// ---- split-KV paged decode attention ---------------------------------------
+// (gt, tiles, blocks) of the first kernel's grid: the launcher's own plan.
+std::tuple<int64_t, int64_t, int64_t> decode_attn_split_grid(
+    int64_t b, int64_t h, int64_t hkv, int64_t num_splits, bool int8) {
+  TORCH_CHECK(b >= 0 && h > 0 && hkv > 0 && h % hkv == 0 && num_splits >= 1,
+              "decode_attn_split_grid: need H % HKV == 0 and num_splits >= 1");
+  const pa::DecodeAttnSplitPlan p =
+      pa::decode_attn_split_plan(b, h, hkv, num_splits, int8);
+  return {p.gt, p.tiles, p.blocks};
+}
+
+// Contract (docs/KERNELS.md "split-KV decode attention"): the
+// decode_attention_int8 contract with scales, its analogue for bf16 caches
+// without; 1 <= num_splits <= 64.  Every check precedes any launch.
+Tensor decode_attention_split(const Tensor& q, const Tensor& kcache,
+                              const Tensor& vcache, const Tensor& block_table,
+                              const Tensor& seq_lens, double scale,
+                              int64_t num_splits,
+                              const c10::optional<Tensor>& k_scale,
+                              const c10::optional<Tensor>& v_scale) {
+  const char* op = "decode_attention_split";
+  TORCH_CHECK(q.is_cuda(), op, ": q must be a GPU tensor");
+  TORCH_CHECK(k_scale.has_value() == v_scale.has_value(), op,
+              ": give both k_scale and v_scale or neither");
+  const bool int8 = k_scale.has_value();
+  bool per_token = false;
+  if (int8) {
+    per_token = check_kv_int8_pools(kcache, vcache, *k_scale, *v_scale,
+                                    q.device(), op);
+  } else {
+    for (const Tensor* t : {&kcache, &vcache})
+      TORCH_CHECK(t->is_cuda() && t->device() == q.device(), op,
+                  ": all tensors must be on one GPU");
+    TORCH_CHECK(kcache.scalar_type() == torch::kBFloat16 &&
+                vcache.scalar_type() == torch::kBFloat16, op,
+                ": caches must be bfloat16 (or int8 with scales)");
+    TORCH_CHECK(kcache.dim() == 4 && kcache.is_contiguous() &&
+                vcache.is_contiguous() && kcache.sizes() == vcache.sizes(), op,
+                ": caches must be contiguous [nblocks, block_size, HKV, D] of "
+                "equal shape");
+    TORCH_CHECK(kcache.size(3) == 64 || kcache.size(3) == 128, op,
+                ": D must be 64 or 128, got ", kcache.size(3));
+    TORCH_CHECK(kcache.numel() > 0, op, ": empty cache");
+  }
+  for (const Tensor* t : {&kcache, &vcache})
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(t->const_data_ptr()) % 16 == 0, op,
+                ": caches must start 16-byte aligned");
+  TORCH_CHECK(q.scalar_type() == torch::kBFloat16 && q.dim() == 3 &&
+              q.is_contiguous(), op, ": q must be contiguous bfloat16 [B, H, D]");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(q.const_data_ptr()) % 16 == 0, op,
+              ": q must start 16-byte aligned");
+  const int64_t b = q.size(0), h = q.size(1), d = q.size(2);
+  const int64_t nblocks = kcache.size(0), bs = kcache.size(1),
+                hkv = kcache.size(2);
+  TORCH_CHECK(kcache.size(3) == d, op, ": cache D ", kcache.size(3),
+              " != q D ", d);
+  TORCH_CHECK(h > 0 && h % hkv == 0, op, ": H % HKV != 0 (", h, ", ", hkv, ")");
+  TORCH_CHECK(block_table.is_cuda() && block_table.device() == q.device() &&
+              block_table.scalar_type() == torch::kInt &&
+              block_table.dim() == 2 && block_table.size(0) == b &&
+              block_table.is_contiguous(), op,
+              ": block_table must be contiguous int32 [B, max_blocks]");
+  TORCH_CHECK(seq_lens.is_cuda() && seq_lens.device() == q.device() &&
+              seq_lens.scalar_type() == torch::kInt && seq_lens.dim() == 1 &&
+              seq_lens.size(0) == b && seq_lens.is_contiguous(), op,
+              ": seq_lens must be contiguous int32 [B]");
+  TORCH_CHECK(num_splits >= 1 && num_splits <= 64, op,
+              ": num_splits must be in [1, 64], got ", num_splits);
+  // the slice rule rounds S up by at most 64 * num_splits in int32
+  TORCH_CHECK(nblocks < (1LL << 31) && b * h < (1LL << 31) / 64 &&
+              block_table.size(1) * bs < (1LL << 31) - 64 * 64, op,
+              ": size overflow");
+  auto o = torch::empty_like(q);
+  auto fopt = q.options().dtype(torch::kFloat);
+  auto o_part = torch::empty({b, h, num_splits, d}, fopt);
+  auto ml_part = torch::empty({b, h, num_splits, 2}, fopt);
+  pa::decode_attention_split(
+      q.const_data_ptr(), kcache.const_data_ptr(), vcache.const_data_ptr(),
+      int8 ? k_scale->const_data_ptr<float>() : nullptr,
+      int8 ? v_scale->const_data_ptr<float>() : nullptr,
+      block_table.const_data_ptr<int>(), seq_lens.const_data_ptr<int>(),
+      o.mutable_data_ptr(), o_part.mutable_data_ptr<float>(),
+      ml_part.mutable_data_ptr<float>(), b, h, hkv, bs, block_table.size(1),
+      nblocks, d, (float)scale, num_splits, per_token ? bs * hkv : 0,
+      per_token ? hkv : 0, 1, cur_stream());
+  return o;
+}
+
 // ---- hand-written GEMM ----------------------------------------------------
 Tensor gemm_bf16(const Tensor& a, const Tensor& b, bool b_is_nt) {
   TORCH_CHECK(a.is_cuda() && a.scalar_type() == torch::kBFloat16);
@@ -1334,6 +1422,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("kcache"), py::arg("vcache"), py::arg("kscale"),
         py::arg("vscale"), py::arg("block_table"), py::arg("seq_lens"),
         py::arg("scale"));
+  m.def("decode_attention_split", &decode_attention_split, py::arg("q"),
+        py::arg("kcache"), py::arg("vcache"), py::arg("block_table"),
+        py::arg("seq_lens"), py::arg("scale"), py::arg("num_splits"),
+        py::arg("k_scale") = c10::nullopt, py::arg("v_scale") = c10::nullopt);
+  m.def("decode_attn_split_grid", &decode_attn_split_grid, py::arg("b"),
+        py::arg("h"), py::arg("hkv"), py::arg("num_splits"), py::arg("int8"));
   m.def("mfma_probe", &mfma_probe);
   m.def("mfma_probe32", &mfma_probe32);
   m.attr("compiled_arch") = "gfx950";

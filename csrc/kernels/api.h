@@ -211,6 +211,33 @@ void decode_attention_int8(const void* q, const void* kcache,
                            int64_t ss_blk, int64_t ss_pos, int64_t ss_head,
                            hipStream_t s);
 
+// ---- split-KV paged decode attention (decode_attn_split.hip) ---------------
+// One block per (split, head tile, kv head, sequence): a tile of `gt`
+// consecutive q-heads of one kv head's group G = H/HKV shares each K/V load,
+// `tiles` = ceil(G / gt) tiles per kv head, grid = b * hkv * tiles * nsplit
+// blocks.  gt is the smallest instantiated tile >= G, at most 8 (bf16
+// cache) or 4 (int8 cache).
+struct DecodeAttnSplitPlan { int gt, tiles; int64_t blocks; };
+DecodeAttnSplitPlan decode_attn_split_plan(int64_t b, int64_t h, int64_t hkv,
+                                           int64_t nsplit, bool int8);
+// Default paged layout [nblocks, bs, HKV, D] only.  kscale/vscale null: bf16
+// cache; else int8 codes with scale strides as decode_attention_int8.
+// Slice rule, on the device: S_b = min(seq_lens[b], max_blocks * bs),
+// c_b = 64 * ceil(S_b / (64 * nsplit)), split s covers
+// [s * c_b, min(S_b, (s + 1) * c_b)).  Workspaces fp32:
+// o_part [B, H, nsplit, D] (unnormalised, relative to the split's max),
+// ml_part [B, H, nsplit, 2] (max, sum); every element is written by the
+// first kernel before the merge kernel reads it.  1 <= nsplit <= 64.
+void decode_attention_split(const void* q, const void* kcache,
+                            const void* vcache, const float* kscale,
+                            const float* vscale, const int* block_table,
+                            const int* seq_lens, void* o, float* o_part,
+                            float* ml_part, int64_t b, int64_t h, int64_t hkv,
+                            int64_t bs, int64_t max_blocks, int64_t nblocks,
+                            int64_t dh, float scale, int64_t nsplit,
+                            int64_t ss_blk, int64_t ss_pos, int64_t ss_head,
+                            hipStream_t s);
+
 // ---- hand-written bf16 MFMA GEMM (C[m][n] = op(A) x op(B)) ----------------
 // b_is_nt: B passed as Bt[n][k] row-major (fast path); else B[k][n].
 void gemm_bf16_8p(const void* a, const void* b, void* c, int64_t m, int64_t n,

@@ -70,9 +70,12 @@ class PagedKVCache:
 
 @torch.no_grad()
 def generate_gpt(model, input_ids, max_new_tokens=16, cache_blocks=None,
-                 block_size=16, greedy=True, kv_cache="bf16"):
+                 block_size=16, greedy=True, kv_cache="bf16",
+                 decode_splits=None):
     """Greedy/sampled generation for GPTForPretraining with paged KV
-    (kv_cache="int8": int8 codes + per-token scales, see PagedKVCache)."""
+    (kv_cache="int8": int8 codes + per-token scales, see PagedKVCache).
+    decode_splits is paged_decode_attention's num_splits: None = shape
+    heuristic, 0 = one-block-per-q-head kernels, n >= 1 = split-KV kernels."""
     model.eval()
     cfg = model.cfg
     B, S0 = input_ids.shape
@@ -123,7 +126,8 @@ def generate_gpt(model, input_ids, max_new_tokens=16, cache_blocks=None,
             att = hot.paged_decode_attention(
                 q.reshape(B, H, D), cache.k[li], cache.v[li],
                 cache.block_table, cache_lens, scale,
-                k_scale=cache.k_scale[li], v_scale=cache.v_scale[li])
+                k_scale=cache.k_scale[li], v_scale=cache.v_scale[li],
+                num_splits=decode_splits)
             att = layer.attn.out_proj(att.reshape(B, 1, H * D))
             x = x + att
             x = x + layer.mlp(layer.ln2(x))
@@ -133,11 +137,14 @@ def generate_gpt(model, input_ids, max_new_tokens=16, cache_blocks=None,
 
 
 def generate_llama(model, input_ids, max_new_tokens=16, cache_blocks=None,
-                   block_size=16, greedy=True, kv_cache="bf16"):
+                   block_size=16, greedy=True, kv_cache="bf16",
+                   decode_splits=None):
     """Greedy/sampled generation for LlamaForCausalLM with a paged GQA KV
     cache: rope applied at the absolute position, K/V cached at
     num_kv_heads, paged decode attention broadcasting HKV -> H
     (decode_attn.hip handles the head mapping in-kernel).
+
+    decode_splits is paged_decode_attention's num_splits (see generate_gpt).
 
     Reference role: the PaddleNLP llama generation loop over the paged
     block_multihead path; re-derived here against models/llama.py."""
@@ -197,7 +204,8 @@ def generate_llama(model, input_ids, max_new_tokens=16, cache_blocks=None,
             att = hot.paged_decode_attention(
                 q.reshape(B, H, D), cache.k[li], cache.v[li],
                 cache.block_table, cache_lens, scale,
-                k_scale=cache.k_scale[li], v_scale=cache.v_scale[li])
+                k_scale=cache.k_scale[li], v_scale=cache.v_scale[li],
+                num_splits=decode_splits)
             x = x + layer.self_attn.o_proj(att.reshape(B, 1, H * D))
             x = x + layer.mlp(layer.post_attention_layernorm(x))
         cache.advance(1)

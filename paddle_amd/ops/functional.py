@@ -1228,16 +1228,129 @@ def _kv_int8_dequant_rows(cache, sc, blocks, S):
     return x * sc.reshape(1, hkv, 1)
 
 
+# Split-KV decode attention (docs/KERNELS.md "split-KV decode attention").
+# The plan sees shapes only, never seq_lens, so a captured graph keeps its
+# kernels whatever the lengths become.
+# Blocks the split grid aims at, by head tile GT: about the blocks 256 CUs
+# hold at each variant's occupancy (8 | 5 | 3..2 | 1 waves per SIMD), fitted
+# to the sweep in profiles/decode_attn_split.txt.
+_DECODE_ATTN_SPLIT_TARGET = {1: 2048, 2: 1024, 4: 512, 8: 512}
+# B * H blocks of the one-block-per-q-head kernels that already fill the
+# device: at or above it those kernels stay (B32 H32, with or without GQA)
+_DECODE_ATTN_SPLIT_FULL = 512
+_DECODE_ATTN_SPLIT_MIN_CAPACITY = 512  # below: today's kernels, always
+_DECODE_ATTN_SPLIT_MIN_SLICE = 256     # positions of capacity per split
+_DECODE_ATTN_SPLIT_PLAN_MAX = 32       # the heuristic's cap (sweep: 1..32)
+_DECODE_ATTN_SPLIT_MAX = 64            # the binding's cap
+
+
+def _decode_attn_split_tiles(H, HKV, int8):
+    """(GT, tiles per kv head) of decode_attention_split: the smallest
+    instantiated head tile >= G = H/HKV, at most 8 (bf16) or 4 (int8)."""
+    g = H // HKV
+    gt = 1
+    while gt < g and gt < (4 if int8 else 8):
+        gt *= 2
+    return gt, -(-g // gt)
+
+
+def _decode_attn_split_plan(B, H, HKV, D, capacity, int8):
+    """Number of KV splits for a default paged_decode_attention call
+    (pure; capacity = max_blocks * block_size).  1 means today's kernels.
+    1 whenever capacity < 512, whenever today's grid B * H reaches 512
+    blocks, and whenever the unsplit grid B * HKV * tiles already reaches
+    the block target of its head tile; else enough splits to reach that
+    target, each covering at least 256 positions of capacity, at most 32."""
+    if capacity < _DECODE_ATTN_SPLIT_MIN_CAPACITY or B <= 0 or HKV <= 0 \
+            or H <= 0 or H % HKV:
+        return 1
+    if B * H >= _DECODE_ATTN_SPLIT_FULL:
+        return 1
+    gt, tiles = _decode_attn_split_tiles(H, HKV, int8)
+    target = _DECODE_ATTN_SPLIT_TARGET[gt]
+    blocks = B * HKV * tiles
+    if blocks >= target:
+        return 1
+    n = min(capacity // _DECODE_ATTN_SPLIT_MIN_SLICE, -(-target // blocks),
+            _DECODE_ATTN_SPLIT_PLAN_MAX)
+    return max(int(n), 1)
+
+
+def _decode_attn_split_native_ok(q, k_cache, v_cache, block_table, seq_lens,
+                                 k_scale=None, v_scale=None):
+    """Contract of decode_attention_split (pure: dtypes, shapes, strides,
+    devices).  With scales: _kv_int8_native_ok.  Without: bf16 contiguous
+    [nblocks, bs, HKV, D] caches of equal shape on q's device, q bf16
+    [B, H, D] (the dispatch site passes it contiguous) 16-byte aligned,
+    D in {64, 128} equal to the cache's, H % HKV == 0, block_table
+    [B, max_blocks] and seq_lens [B] integer tensors (the site casts them to
+    int32)."""
+    if (k_scale is None) != (v_scale is None):
+        return False
+    if k_scale is not None:
+        return _kv_int8_native_ok(q, k_cache, v_cache, k_scale, v_scale,
+                                  block_table, seq_lens)
+    ts = (q, k_cache, v_cache, block_table, seq_lens)
+    if not all(isinstance(t, torch.Tensor) for t in ts):
+        return False
+    if any(t.device != q.device for t in ts):
+        return False
+    if not (q.dtype == torch.bfloat16 and q.dim() == 3
+            and k_cache.dtype == torch.bfloat16
+            and v_cache.dtype == torch.bfloat16 and k_cache.dim() == 4
+            and k_cache.shape == v_cache.shape and k_cache.is_contiguous()
+            and v_cache.is_contiguous() and k_cache.numel() > 0
+            and (k_cache.storage_offset() * 2) % 16 == 0
+            and (v_cache.storage_offset() * 2) % 16 == 0):
+        return False
+    b, h, d = q.shape
+    if d not in (64, 128) or d != k_cache.shape[3] or h == 0 \
+            or h % k_cache.shape[2]:
+        return False
+    if q.is_contiguous() and (q.storage_offset() * 2) % 16:
+        return False
+    ints = (torch.int32, torch.int64)
+    return (block_table.dim() == 2 and block_table.shape[0] == b
+            and block_table.dtype in ints and seq_lens.dim() == 1
+            and seq_lens.shape[0] == b and seq_lens.dtype in ints)
+
+
 def paged_decode_attention(q, k_cache, v_cache, block_table, seq_lens, scale=None,
-                           k_scale=None, v_scale=None):
+                           k_scale=None, v_scale=None, num_splits=None):
     """One decode step. q: [B, H, D]; k/v_cache: [nblocks, block_size, HKV, D];
     block_table: int32 [B, max_blocks]; seq_lens: int32 [B].
     With k_scale/v_scale the caches are int8 code pools (docs/KERNELS.md
     "int8 KV cache"): fp32 scales [nblocks, block_size, HKV] (per token, as
-    kv_cache_quant_append writes them) or [HKV] (per head)."""
+    kv_cache_quant_append writes them) or [HKV] (per head).
+    num_splits chooses the kernels (docs/KERNELS.md "split-KV decode
+    attention"): None asks _decode_attn_split_plan, whose answer 1 means
+    the one-block-per-q-head kernels; 0 pins those kernels; n >= 1 forces
+    the split-KV kernels with n splits (n = 1: group sharing alone).
+    Outside the split kernels' contract, on CPU or with native kernels off,
+    num_splits is ignored."""
     if scale is None:
         scale = 1.0 / math.sqrt(q.shape[-1])
     int8 = k_scale is not None or v_scale is not None
+    if num_splits is not None and (int(num_splits) != num_splits
+                                   or not 0 <= num_splits
+                                   <= _DECODE_ATTN_SPLIT_MAX):
+        raise ValueError("paged_decode_attention: num_splits must be None or "
+                         f"an integer in [0, {_DECODE_ATTN_SPLIT_MAX}], got "
+                         f"{num_splits!r}")
+    if num_splits != 0 and (not int8 or (k_scale is not None
+                                         and v_scale is not None)) \
+            and _ext.use_native(q) and _decode_attn_split_native_ok(
+                q, k_cache, v_cache, block_table, seq_lens, k_scale, v_scale):
+        n = num_splits
+        if n is None:
+            n = _decode_attn_split_plan(
+                q.shape[0], q.shape[1], k_cache.shape[2], q.shape[2],
+                block_table.shape[1] * k_cache.shape[1], int8)
+        if num_splits is not None or n > 1:
+            return _ext.get_ext().decode_attention_split(
+                q.contiguous(), k_cache, v_cache,
+                block_table.int().contiguous(), seq_lens.int().contiguous(),
+                scale, int(n), k_scale, v_scale)
     if int8:
         if k_scale is None or v_scale is None:
             raise ValueError("paged_decode_attention: give both k_scale and "

@@ -238,11 +238,22 @@ class GPTModelRunner:
     def __init__(self, model, num_blocks=1024, block_size=16,
                  device=None, dtype=None, max_seq=2048, use_graphs=True,
                  weight_only=False, weight_only_group_size=-1,
-                 kv_cache="bf16"):
+                 kv_cache="bf16", decode_splits=None):
         import math
         from .ops import functional as hot
         self.hot = hot
         self.model = model.eval()
+        # decode_splits -> paged_decode_attention(num_splits=): None lets the
+        # shape heuristic choose (bucket B and max_seq only, so each bucket's
+        # graph is fixed), 0 pins the one-block-per-q-head kernels, n >= 1
+        # forces the split-KV kernels with n splits (docs/KERNELS.md
+        # "split-KV decode attention")
+        if decode_splits is not None and (
+                int(decode_splits) != decode_splits
+                or not 0 <= decode_splits <= 64):
+            raise ValueError("decode_splits must be None or an integer in "
+                             f"[0, 64], got {decode_splits!r}")
+        self.decode_splits = decode_splits
         # kv_cache="int8": int8 code pools + per-token fp32 scale pools
         # (about half the KV bytes; docs/KERNELS.md "int8 KV cache")
         if kv_cache not in ("bf16", "int8"):
@@ -441,7 +452,8 @@ class GPTModelRunner:
             att = self.hot.paged_decode_attention(
                 q.reshape(B, self.H, self.D), self.k[li], self.v[li],
                 table, lens + 1, self.scale,
-                k_scale=self.k_scale[li], v_scale=self.v_scale[li])
+                k_scale=self.k_scale[li], v_scale=self.v_scale[li],
+                num_splits=self.decode_splits)
             x = x + layer.attn.out_proj(att.reshape(B, 1, -1))
             x = x + layer.mlp(layer.ln2(x))
         return m.lm_head(m.gpt.final_norm(x[:, 0]))
@@ -618,7 +630,8 @@ class LlamaModelRunner(GPTModelRunner):
             att = self.hot.paged_decode_attention(
                 q.reshape(B, self.H, self.D), self.k[li], self.v[li],
                 table, lens + 1, self.scale,
-                k_scale=self.k_scale[li], v_scale=self.v_scale[li])
+                k_scale=self.k_scale[li], v_scale=self.v_scale[li],
+                num_splits=self.decode_splits)
             x = x + layer.self_attn.o_proj(att.reshape(B, 1, -1))
             x = x + layer.mlp(layer.post_attention_layernorm(x))
         return m.lm_head(m.llama.norm(x[:, 0]))

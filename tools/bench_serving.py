@@ -19,7 +19,7 @@ from paddle_amd.serving import Engine, GPTModelRunner, Request  # noqa: E402
 
 def run_one(tag, model, n_req=64, prompt_len=128, gen_len=128, max_batch=32,
             num_blocks=4096, weight_only=False, runner_cls="gpt",
-            group_size=-1, kv_cache="bf16"):
+            group_size=-1, kv_cache="bf16", decode_splits=None):
     cls = GPTModelRunner
     if runner_cls == "llama":
         from paddle_amd.serving import LlamaModelRunner
@@ -27,7 +27,7 @@ def run_one(tag, model, n_req=64, prompt_len=128, gen_len=128, max_batch=32,
     runner = cls(model, num_blocks=num_blocks, block_size=16,
                  max_seq=max(2048, prompt_len + gen_len),
                  weight_only=weight_only, weight_only_group_size=group_size,
-                 kv_cache=kv_cache)
+                 kv_cache=kv_cache, decode_splits=decode_splits)
     pools = runner.k + runner.v + [s for s in runner.k_scale + runner.v_scale
                                    if s is not None]
     pool_gb = sum(t.numel() * t.element_size() for t in pools) / 2**30
@@ -83,6 +83,11 @@ def main():
     ap.add_argument("--prompt-len", type=int, default=128)
     ap.add_argument("--gen-len", type=int, default=128)
     ap.add_argument("--n-req", type=int, default=64)
+    ap.add_argument("--max-batch", type=int, default=32,
+                    help="engine batch limit (and the pre-captured bucket)")
+    ap.add_argument("--decode-splits", type=int, default=None,
+                    help="runner decode_splits: unset = heuristic, 0 = "
+                         "one-block-per-q-head kernels, n = split-KV kernels")
     args = ap.parse_args()
     paddle.seed(0)
     wo = args.weight_only_dtype or ("int8" if args.weight_only else False)
@@ -91,9 +96,14 @@ def main():
         tag_sfx = f" {wo}-wo" + (f"-gs{args.group_size}" if args.group_size > 0 else "")
     if args.kv_cache != "bf16":
         tag_sfx += f" {args.kv_cache}-kv"
+    if args.decode_splits is not None:
+        tag_sfx += f" splits={args.decode_splits}"
+    if args.max_batch != 32:
+        tag_sfx += f" b{args.max_batch}"
     kw = dict(weight_only=wo, group_size=args.group_size,
               kv_cache=args.kv_cache, prompt_len=args.prompt_len,
-              gen_len=args.gen_len, n_req=args.n_req)
+              gen_len=args.gen_len, n_req=args.n_req,
+              max_batch=args.max_batch, decode_splits=args.decode_splits)
     seq = max(2048, args.prompt_len + args.gen_len)
     # blocks for max_batch sequences of prompt+gen tokens, with headroom
     nblk = max(8192, 2 * 32 * (-(-seq // 16)))
@@ -104,12 +114,12 @@ def main():
         run_one("gpt-350M" + tag_sfx, m, **kw)
     elif args.model == "gpt3-6.7b":
         m = build_gpt("gpt3-6.7b", max_seq_len=seq).to("cuda", torch.bfloat16)
-        run_one("gpt3-6.7B" + tag_sfx, m, max_batch=32, num_blocks=nblk, **kw)
+        run_one("gpt3-6.7B" + tag_sfx, m, num_blocks=nblk, **kw)
     else:
         from paddle_amd.models.llama import build_llama
         m = build_llama("llama2-7b", max_seq_len=seq).to("cuda", torch.bfloat16)
-        run_one("llama2-7B" + tag_sfx, m, max_batch=32, num_blocks=nblk,
-                runner_cls="llama", **kw)
+        run_one("llama2-7B" + tag_sfx, m, num_blocks=nblk, runner_cls="llama",
+                **kw)
 
 
 if __name__ == "__main__":
