@@ -708,33 +708,6 @@ Tensor embedding_bwd(const Tensor& dout, const Tensor& ids_in, int64_t vocab,
   return dtable;
 }
 
-// ---- decode attention ------------------------------------------------------
-Tensor decode_attention(const Tensor& q, const Tensor& kcache, const Tensor& vcache,
-                        const Tensor& block_table, const Tensor& seq_lens,
-                        double scale, int64_t blk_str, int64_t pos_str,
-                        int64_t head_str, int64_t bs_override) {
-  CHECK_IN(q); CHECK_IN(kcache); CHECK_IN(vcache);
-  TORCH_CHECK(q.dim() == 3, "q: [B, H, D] (one decode step)");
-  int64_t b = q.size(0), h = q.size(1), d = q.size(2);
-  int64_t bs, hkv;
-  if (blk_str == 0) {
-    TORCH_CHECK(kcache.dim() == 4, "k_cache: [nblocks, block_size, HKV, D]");
-    bs = kcache.size(1); hkv = kcache.size(2);
-  } else {
-    bs = bs_override; hkv = bs_override >= 0 ? h : h;  // dense: hkv == h
-    hkv = kcache.size(1) == h ? h : kcache.size(1);
-  }
-  int64_t max_blocks = block_table.size(1);
-  auto o = torch::empty_like(q);
-  pa::decode_attention(q.const_data_ptr(), kcache.const_data_ptr(),
-                       vcache.const_data_ptr(),
-                       block_table.const_data_ptr<int>(),
-                       seq_lens.const_data_ptr<int>(), o.mutable_data_ptr(),
-                       b, h, hkv, bs, max_blocks, d, (float)scale,
-                       blk_str, pos_str, head_str, cur_stream());
-  return o;
-}
-
 // ---- int8 paged KV cache ---------------------------------------------------
 // Contract shared by kv_quant_append and decode_attention_int8 (docs/
 // KERNELS.md): int8 contiguous [nblocks, bs, HKV, D] code pools of equal
@@ -831,67 +804,18 @@ void kv_quant_append(const Tensor& k, const Tensor& v, const Tensor& kcache,
                       v.stride(1), cur_stream());
 }
 
-Tensor decode_attention_int8(const Tensor& q, const Tensor& kcache,
-                             const Tensor& vcache, const Tensor& kscale,
-                             const Tensor& vscale, const Tensor& block_table,
-                             const Tensor& seq_lens, double scale) {
-  const char* op = "decode_attention_int8";
-  TORCH_CHECK(q.is_cuda(), op, ": q must be a GPU tensor");
-  const bool per_token =
-      check_kv_int8_pools(kcache, vcache, kscale, vscale, q.device(), op);
-  TORCH_CHECK(q.scalar_type() == torch::kBFloat16 && q.dim() == 3 &&
-              q.is_contiguous(), op, ": q must be contiguous bfloat16 [B, H, D]");
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(q.const_data_ptr()) % 16 == 0, op,
-              ": q must start 16-byte aligned");
-  const int64_t b = q.size(0), h = q.size(1), d = q.size(2);
-  const int64_t nblocks = kcache.size(0), bs = kcache.size(1),
-                hkv = kcache.size(2);
-  TORCH_CHECK(kcache.size(3) == d, op, ": cache D ", kcache.size(3),
-              " != q D ", d);
-  TORCH_CHECK(h > 0 && h % hkv == 0, op, ": H % HKV != 0 (", h, ", ", hkv, ")");
-  TORCH_CHECK(block_table.is_cuda() && block_table.device() == q.device() &&
-              block_table.scalar_type() == torch::kInt &&
-              block_table.dim() == 2 && block_table.size(0) == b &&
-              block_table.is_contiguous(), op,
-              ": block_table must be contiguous int32 [B, max_blocks]");
-  TORCH_CHECK(seq_lens.is_cuda() && seq_lens.device() == q.device() &&
-              seq_lens.scalar_type() == torch::kInt && seq_lens.dim() == 1 &&
-              seq_lens.size(0) == b && seq_lens.is_contiguous(), op,
-              ": seq_lens must be contiguous int32 [B]");
-  TORCH_CHECK(nblocks < (1LL << 31) && b * h < (1LL << 31) &&
-              block_table.size(1) * bs < (1LL << 31), op, ": size overflow");
-  auto o = torch::empty_like(q);
-  pa::decode_attention_int8(
-      q.const_data_ptr(), kcache.const_data_ptr(), vcache.const_data_ptr(),
-      kscale.const_data_ptr<float>(), vscale.const_data_ptr<float>(),
-      block_table.const_data_ptr<int>(), seq_lens.const_data_ptr<int>(),
-      o.mutable_data_ptr(), b, h, hkv, bs, block_table.size(1), nblocks, d,
-      (float)scale, per_token ? bs * hkv : 0, per_token ? hkv : 0, 1,
-      cur_stream());
-  return o;
-}
-
-// ---- split-KV paged decode attention ---------------------------------------
-// (gt, tiles, blocks) of the first kernel's grid: the launcher's own plan.
-std::tuple<int64_t, int64_t, int64_t> decode_attn_split_grid(
-    int64_t b, int64_t h, int64_t hkv, int64_t num_splits, bool int8) {
-  TORCH_CHECK(b >= 0 && h > 0 && hkv > 0 && h % hkv == 0 && num_splits >= 1,
-              "decode_attn_split_grid: need H % HKV == 0 and num_splits >= 1");
-  const pa::DecodeAttnSplitPlan p =
-      pa::decode_attn_split_plan(b, h, hkv, num_splits, int8);
-  return {p.gt, p.tiles, p.blocks};
-}
-
-// Contract (docs/KERNELS.md "split-KV decode attention"): the
-// decode_attention_int8 contract with scales, its analogue for bf16 caches
-// without; 1 <= num_splits <= 64.  Every check precedes any launch.
-Tensor decode_attention_split(const Tensor& q, const Tensor& kcache,
-                              const Tensor& vcache, const Tensor& block_table,
-                              const Tensor& seq_lens, double scale,
-                              int64_t num_splits,
-                              const c10::optional<Tensor>& k_scale,
-                              const c10::optional<Tensor>& v_scale) {
-  const char* op = "decode_attention_split";
+// ---- paged decode attention ------------------------------------------------
+// The one contract of decode_attention, decode_attention_int8 and
+// decode_attention_split (docs/KERNELS.md "paged decode attention"); returns
+// the launch arguments, to which the caller adds scale, output and
+// workspaces.  Every check precedes any launch.  `dense` is null for the
+// paged layout [nblocks, bs, HKV, D]; else {blk, pos, head, bs}: the caller's
+// element strides and block size over bf16 caches [nblocks, HKV, ., D].
+static pa::DecodeAttnArgs check_paged_decode(
+    const char* op, const Tensor& q, const Tensor& kcache,
+    const Tensor& vcache, const Tensor& block_table, const Tensor& seq_lens,
+    const c10::optional<Tensor>& k_scale, const c10::optional<Tensor>& v_scale,
+    int64_t nsplit, const int64_t* dense = nullptr) {
   TORCH_CHECK(q.is_cuda(), op, ": q must be a GPU tensor");
   TORCH_CHECK(k_scale.has_value() == v_scale.has_value(), op,
               ": give both k_scale and v_scale or neither");
@@ -923,11 +847,28 @@ Tensor decode_attention_split(const Tensor& q, const Tensor& kcache,
   TORCH_CHECK(reinterpret_cast<uintptr_t>(q.const_data_ptr()) % 16 == 0, op,
               ": q must start 16-byte aligned");
   const int64_t b = q.size(0), h = q.size(1), d = q.size(2);
-  const int64_t nblocks = kcache.size(0), bs = kcache.size(1),
-                hkv = kcache.size(2);
+  const int64_t nblocks = kcache.size(0);
+  const int64_t bs = dense ? dense[3] : kcache.size(1);
+  const int64_t hkv = kcache.size(dense ? 1 : 2);
   TORCH_CHECK(kcache.size(3) == d, op, ": cache D ", kcache.size(3),
               " != q D ", d);
   TORCH_CHECK(h > 0 && h % hkv == 0, op, ": H % HKV != 0 (", h, ", ", hkv, ")");
+  int64_t cs[3] = {bs * hkv * d, hkv * d, d};
+  if (dense) {
+    const int64_t n = kcache.numel(), cnt[3] = {nblocks, bs, hkv};
+    TORCH_CHECK(bs > 0, op, ": block size must be positive, got ", bs);
+    // each term of the largest index fits in numel, so their sum cannot wrap
+    for (int i = 0; i < 3; ++i) {
+      cs[i] = dense[i];
+      TORCH_CHECK(cs[i] > 0 && cs[i] % (d / 16) == 0, op,
+                  ": cache strides must be positive multiples of ", d / 16,
+                  " elements, got ", cs[i]);
+      TORCH_CHECK(cnt[i] == 1 || cs[i] <= n / (cnt[i] - 1), op,
+                  ": cache strides index past the cache");
+    }
+    TORCH_CHECK((nblocks - 1) * cs[0] + (bs - 1) * cs[1] + (hkv - 1) * cs[2] +
+                    d <= n, op, ": cache strides index past the cache");
+  }
   TORCH_CHECK(block_table.is_cuda() && block_table.device() == q.device() &&
               block_table.scalar_type() == torch::kInt &&
               block_table.dim() == 2 && block_table.size(0) == b &&
@@ -937,26 +878,92 @@ Tensor decode_attention_split(const Tensor& q, const Tensor& kcache,
               seq_lens.scalar_type() == torch::kInt && seq_lens.dim() == 1 &&
               seq_lens.size(0) == b && seq_lens.is_contiguous(), op,
               ": seq_lens must be contiguous int32 [B]");
+  // int32 on the device; the slice rule rounds S up by at most 64 * nsplit
+  const int64_t lim = 1LL << 31;
+  TORCH_CHECK(nblocks < lim && bs < lim &&
+              b * h < (nsplit ? lim / 64 : lim) &&
+              block_table.size(1) * bs < (nsplit ? lim - 64 * 64 : lim), op,
+              ": size overflow");
+  pa::DecodeAttnArgs a{};
+  a.q = q.const_data_ptr();
+  a.kcache = kcache.const_data_ptr();
+  a.vcache = vcache.const_data_ptr();
+  a.kscale = int8 ? k_scale->const_data_ptr<float>() : nullptr;
+  a.vscale = int8 ? v_scale->const_data_ptr<float>() : nullptr;
+  a.block_table = block_table.const_data_ptr<int>();
+  a.seq_lens = seq_lens.const_data_ptr<int>();
+  a.b = (int)b; a.h = (int)h; a.hkv = (int)hkv; a.bs = (int)bs;
+  a.max_blocks = (int)block_table.size(1);
+  a.nblocks = (int)nblocks; a.dh = (int)d; a.nsplit = (int)nsplit;
+  a.cs_blk = cs[0]; a.cs_pos = cs[1]; a.cs_head = cs[2];
+  a.ss_blk = per_token ? bs * hkv : 0;
+  a.ss_pos = per_token ? hkv : 0;
+  a.ss_head = 1;
+  return a;
+}
+
+static Tensor launch_paged_decode(pa::DecodeAttnArgs a, const Tensor& q,
+                                  double scale) {
+  auto o = torch::empty_like(q);
+  Tensor o_part, ml_part;
+  if (a.nsplit > 0) {
+    auto fopt = q.options().dtype(torch::kFloat);
+    o_part = torch::empty({a.b, a.h, a.nsplit, a.dh}, fopt);
+    ml_part = torch::empty({a.b, a.h, a.nsplit, 2}, fopt);
+    a.o_part = o_part.mutable_data_ptr<float>();
+    a.ml_part = ml_part.mutable_data_ptr<float>();
+  }
+  a.o = o.mutable_data_ptr();
+  a.scale = (float)scale;
+  pa::decode_attention(a, cur_stream());
+  return o;
+}
+
+// blk_str = pos_str = head_str = bs = 0: paged bf16 caches; else the dense
+// layout by the caller's strides (masked_multihead_attention).
+Tensor decode_attention(const Tensor& q, const Tensor& kcache,
+                        const Tensor& vcache, const Tensor& block_table,
+                        const Tensor& seq_lens, double scale, int64_t blk_str,
+                        int64_t pos_str, int64_t head_str, int64_t bs) {
+  const int64_t dense[4] = {blk_str, pos_str, head_str, bs};
+  const bool paged = !blk_str && !pos_str && !head_str && !bs;
+  return launch_paged_decode(
+      check_paged_decode("decode_attention", q, kcache, vcache, block_table,
+                         seq_lens, c10::nullopt, c10::nullopt, 0,
+                         paged ? nullptr : dense), q, scale);
+}
+
+Tensor decode_attention_int8(const Tensor& q, const Tensor& kcache,
+                             const Tensor& vcache, const Tensor& kscale,
+                             const Tensor& vscale, const Tensor& block_table,
+                             const Tensor& seq_lens, double scale) {
+  return launch_paged_decode(
+      check_paged_decode("decode_attention_int8", q, kcache, vcache,
+                         block_table, seq_lens, kscale, vscale, 0), q, scale);
+}
+
+// (gt, tiles, blocks) of the split kernel's grid: the launcher's own plan.
+std::tuple<int64_t, int64_t, int64_t> decode_attn_split_grid(
+    int64_t b, int64_t h, int64_t hkv, int64_t num_splits, bool int8) {
+  TORCH_CHECK(b >= 0 && h > 0 && hkv > 0 && h % hkv == 0 && num_splits >= 1,
+              "decode_attn_split_grid: need H % HKV == 0 and num_splits >= 1");
+  const pa::DecodeAttnSplitPlan p =
+      pa::decode_attn_split_plan(b, h, hkv, num_splits, int8);
+  return {p.gt, p.tiles, p.blocks};
+}
+
+Tensor decode_attention_split(const Tensor& q, const Tensor& kcache,
+                              const Tensor& vcache, const Tensor& block_table,
+                              const Tensor& seq_lens, double scale,
+                              int64_t num_splits,
+                              const c10::optional<Tensor>& k_scale,
+                              const c10::optional<Tensor>& v_scale) {
+  const char* op = "decode_attention_split";
   TORCH_CHECK(num_splits >= 1 && num_splits <= 64, op,
               ": num_splits must be in [1, 64], got ", num_splits);
-  // the slice rule rounds S up by at most 64 * num_splits in int32
-  TORCH_CHECK(nblocks < (1LL << 31) && b * h < (1LL << 31) / 64 &&
-              block_table.size(1) * bs < (1LL << 31) - 64 * 64, op,
-              ": size overflow");
-  auto o = torch::empty_like(q);
-  auto fopt = q.options().dtype(torch::kFloat);
-  auto o_part = torch::empty({b, h, num_splits, d}, fopt);
-  auto ml_part = torch::empty({b, h, num_splits, 2}, fopt);
-  pa::decode_attention_split(
-      q.const_data_ptr(), kcache.const_data_ptr(), vcache.const_data_ptr(),
-      int8 ? k_scale->const_data_ptr<float>() : nullptr,
-      int8 ? v_scale->const_data_ptr<float>() : nullptr,
-      block_table.const_data_ptr<int>(), seq_lens.const_data_ptr<int>(),
-      o.mutable_data_ptr(), o_part.mutable_data_ptr<float>(),
-      ml_part.mutable_data_ptr<float>(), b, h, hkv, bs, block_table.size(1),
-      nblocks, d, (float)scale, num_splits, per_token ? bs * hkv : 0,
-      per_token ? hkv : 0, 1, cur_stream());
-  return o;
+  return launch_paged_decode(
+      check_paged_decode(op, q, kcache, vcache, block_table, seq_lens, k_scale,
+                         v_scale, num_splits), q, scale);
 }
 
 // ---- hand-written GEMM ----------------------------------------------------

@@ -177,17 +177,7 @@ void embedding_bwd(const void* dout, const int64_t* ids, float* dtable,
                    int64_t n_ids, int64_t d, int64_t vocab, int64_t padding_idx,
                    int dtype, hipStream_t s);
 
-// ---- paged-KV decode attention (serving) ----------------------------------
-// blk/pos/head strides in elements (0,0,0 = default paged layout
-// [nblocks, bs, HKV, D]); dense [B, H, S, D] caches pass their own
-void decode_attention(const void* q, const void* kcache, const void* vcache,
-                      const int* block_table, const int* seq_lens, void* o,
-                      int64_t b, int64_t h, int64_t hkv, int64_t bs,
-                      int64_t max_blocks, int64_t dh, float scale,
-                      int64_t blk_str, int64_t pos_str, int64_t head_str,
-                      hipStream_t s);
-
-// ---- int8 paged KV cache ---------------------------------------------------
+// ---- int8 paged KV cache: quantize-on-append --------------------------------
 // codes int8 [nblocks, bs, HKV, D]; scales fp32 addressed (blk, pos, head)
 // by element strides: per token [nblocks, bs, HKV] -> (bs*HKV, HKV, 1), per
 // head [HKV] -> (0, 0, 1).
@@ -202,41 +192,41 @@ void kv_quant_append(const void* k, const void* v, void* kcache, void* vcache,
                      int64_t bs, int64_t nblocks, int64_t k_tstr,
                      int64_t k_hstr, int64_t v_tstr, int64_t v_hstr,
                      hipStream_t s);
-void decode_attention_int8(const void* q, const void* kcache,
-                           const void* vcache, const float* kscale,
-                           const float* vscale, const int* block_table,
-                           const int* seq_lens, void* o, int64_t b, int64_t h,
-                           int64_t hkv, int64_t bs, int64_t max_blocks,
-                           int64_t nblocks, int64_t dh, float scale,
-                           int64_t ss_blk, int64_t ss_pos, int64_t ss_head,
-                           hipStream_t s);
 
-// ---- split-KV paged decode attention (decode_attn_split.hip) ---------------
-// One block per (split, head tile, kv head, sequence): a tile of `gt`
-// consecutive q-heads of one kv head's group G = H/HKV shares each K/V load,
-// `tiles` = ceil(G / gt) tiles per kv head, grid = b * hkv * tiles * nsplit
-// blocks.  gt is the smallest instantiated tile >= G, at most 8 (bf16
-// cache) or 4 (int8 cache).
+// ---- paged decode attention (decode_attn.hip) ------------------------------
+// One kernel for every path.  A block owns (split, head tile, kv head,
+// sequence): a tile of `gt` consecutive q-heads of one kv head's group
+// G = H/HKV shares each K/V load, `tiles` = ceil(G / gt) tiles per kv head.
+// Split launches (nsplit >= 1) take gt and the grid from
+// decode_attn_split_plan: gt is the smallest instantiated tile >= G, at most
+// 8 (bf16 cache) or 4 (int8 cache), grid = b * hkv * tiles * nsplit blocks.
+// Unsplit launches (nsplit == 0) use gt = 1, one block per (b, q-head).
 struct DecodeAttnSplitPlan { int gt, tiles; int64_t blocks; };
 DecodeAttnSplitPlan decode_attn_split_plan(int64_t b, int64_t h, int64_t hkv,
                                            int64_t nsplit, bool int8);
-// Default paged layout [nblocks, bs, HKV, D] only.  kscale/vscale null: bf16
-// cache; else int8 codes with scale strides as decode_attention_int8.
-// Slice rule, on the device: S_b = min(seq_lens[b], max_blocks * bs),
-// c_b = 64 * ceil(S_b / (64 * nsplit)), split s covers
-// [s * c_b, min(S_b, (s + 1) * c_b)).  Workspaces fp32:
-// o_part [B, H, nsplit, D] (unnormalised, relative to the split's max),
-// ml_part [B, H, nsplit, 2] (max, sum); every element is written by the
-// first kernel before the merge kernel reads it.  1 <= nsplit <= 64.
-void decode_attention_split(const void* q, const void* kcache,
-                            const void* vcache, const float* kscale,
-                            const float* vscale, const int* block_table,
-                            const int* seq_lens, void* o, float* o_part,
-                            float* ml_part, int64_t b, int64_t h, int64_t hkv,
-                            int64_t bs, int64_t max_blocks, int64_t nblocks,
-                            int64_t dh, float scale, int64_t nsplit,
-                            int64_t ss_blk, int64_t ss_pos, int64_t ss_head,
-                            hipStream_t s);
+// q, o bf16 [b, h, dh] contiguous; block_table int32 [b, max_blocks];
+// seq_lens int32 [b].  kscale/vscale null: bf16 cache; else int8 codes with
+// fp32 scales.  Codes and scales are addressed (blk, pos, head) by element
+// strides cs_* / ss_*; a table entry outside [0, nblocks) reads nothing.
+// S_b = max(0, min(seq_lens[b], max_blocks * bs)).
+// nsplit == 0: one pass over [0, S_b) writes o; no workspace.
+// 1 <= nsplit <= 64: slice rule on the device, c_b = 64 * ceil(S_b / (64 *
+// nsplit)), split s covers [s * c_b, min(S_b, (s + 1) * c_b)); fp32
+// workspaces o_part [b, h, nsplit, dh] (unnormalised, relative to the
+// split's max) and ml_part [b, h, nsplit, 2] (max, sum) are written in full
+// by the first kernel before the merge kernel reads them.
+struct DecodeAttnArgs {
+  const void *q, *kcache, *vcache;
+  const float *kscale, *vscale;
+  const int *block_table, *seq_lens;
+  void* o;
+  float *o_part, *ml_part;
+  int b, h, hkv, bs, max_blocks, nblocks, dh, nsplit;
+  float scale;
+  long long cs_blk, cs_pos, cs_head;
+  long long ss_blk, ss_pos, ss_head;
+};
+void decode_attention(const DecodeAttnArgs& a, hipStream_t s);
 
 // ---- hand-written bf16 MFMA GEMM (C[m][n] = op(A) x op(B)) ----------------
 // b_is_nt: B passed as Bt[n][k] row-major (fast path); else B[k][n].

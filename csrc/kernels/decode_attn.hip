@@ -1,174 +1,36 @@
-// Paged-KV single-token decode attention for gfx950 (serving path).
+// Paged-KV single-token decode attention for gfx950 (serving path;
+// docs/KERNELS.md "paged decode attention") and the int8 KV cache's
+// quantize-on-append.
 //
 // Reference role parity: paddle/phi/kernels/fusion/gpu/
 // masked_multihead_attention_kernel.cu + block_multi_head_attention
-// (paged "block" KV cache) -- re-derived for wave64:
-//   * one 256-thread block per (batch, q-head); GQA via head mapping
-//   * KV streamed from a paged cache: k/v_cache [nblocks, bs, hkv, D],
-//     block_table [B, max_blocks] -- HBM-bound, 16B/lane loads
-//   * 16 lanes per position (D<=128: 8 elems/lane), 4 pos/wave/step,
-//     online softmax in registers, cross-wave merge via LDS
+// (paged "block" KV cache) -- re-derived for wave64.
+//
+// One kernel template serves the bf16 and int8 caches, the paged and the
+// dense layout, unsplit and split-KV.  A 256-thread block owns
+// (split s, head tile, kv head, sequence b):
+//   * a tile of GT consecutive q-heads of one kv head's group shares each
+//     K/V register load (qv/oacc/m/l per head), so rows are fetched once
+//     per tile instead of once per q-head;
+//   * PARTIAL: the positions of a sequence are cut into nsplit slices by a
+//     rule evaluated on the device from seq_lens, so captured graphs stay
+//     valid; partials (max, sum, unnormalised o) go to fp32 workspaces with
+//     plain vector stores, and decode_attn_merge_kernel combines them in a
+//     fixed order -- no atomics, no cross-workgroup flags, same bits every
+//     run;
+//   * !PARTIAL: the block walks [0, S) and writes bf16 o itself.
+// Lane layout per position: bf16 cache 16 lanes x D/16 elements (16
+// positions per block step), int8 cache D/16 lanes x 16 codes (32 | 64
+// positions per block step), 16 B per lane in flight (8 B at bf16 D = 64);
+// next step's loads are issued before this step's math; online softmax in
+// registers with a finite -1e30 sentinel; the block's position slots merge
+// through LDS in slot order.
+#include <type_traits>
+
 #include "common.h"
 #include "api.h"
 
 namespace pa {
-
-template <int D>
-__launch_bounds__(256)
-__global__ void decode_attn_kernel(const short* __restrict__ qg,
-                                   const short* __restrict__ kcache,
-                                   const short* __restrict__ vcache,
-                                   const int* __restrict__ block_table,
-                                   const int* __restrict__ seq_lens,
-                                   short* __restrict__ og,
-                                   int B, int H, int HKV, int bs,
-                                   int max_blocks, float scale,
-                                   long long blk_str, long long pos_str,
-                                   long long head_str) {
-  const int b = blockIdx.x / H;
-  const int h = blockIdx.x % H;
-  const int hkv = h / (H / HKV);
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wid = tid >> 6;
-  const int l16 = lane & 15;   // element group within D
-  const int lp = lane >> 4;    // 0..3: position slot within wave
-  const int S = seq_lens[b];
-
-  // q for this (b,h): D elems; 16-lane group covers D -> E = D/16 per lane
-  constexpr int E = D / 16;
-  float qv[E];
-  {
-    const short* qp = qg + ((long long)b * H + h) * D;
-#pragma unroll
-    for (int i = 0; i < E; ++i) qv[i] = bf2f(qp[l16 * E + i]);
-  }
-
-  float m = -1e30f, l = 0.f;  // finite sentinel: -ffast-math breaks +-inf
-  float oacc[E];
-#pragma unroll
-  for (int i = 0; i < E; ++i) oacc[i] = 0.f;
-
-  // each wave processes 4 positions per step; 4 waves -> 16 pos/block/step.
-  // Software-pipelined: K/V for step t+1 load while step t computes --
-  // the serial position walk was latency-bound (back-to-back dependent
-  // 16 B loads per step).
-  auto load_kv = [&](int pos0, bool& ok, shortx8& kv8, shortx8& vv8) {
-    int pos = pos0 + lp;
-    ok = pos < S;
-    int phys = 0, off = 0;
-    if (ok) {
-      phys = block_table[(long long)b * max_blocks + pos / bs];
-      off = pos % bs;
-    }
-    const long long base = (long long)phys * blk_str +
-                           (long long)off * pos_str +
-                           (long long)hkv * head_str + l16 * E;
-    if (ok) {
-      if (E == 8) {
-        kv8 = *reinterpret_cast<const shortx8*>(kcache + base);
-        vv8 = *reinterpret_cast<const shortx8*>(vcache + base);
-      } else {
-        shortx4 k4 = *reinterpret_cast<const shortx4*>(kcache + base);
-        shortx4 v4 = *reinterpret_cast<const shortx4*>(vcache + base);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { kv8[i] = k4[i]; vv8[i] = v4[i]; }
-      }
-    }
-  };
-
-  bool okc = false, okn = false;
-  shortx8 kc8, vc8, kn8, vn8;
-  const int p_start = wid * 4;
-  load_kv(p_start, okc, kc8, vc8);
-  for (int pos0 = p_start; pos0 < S; pos0 += 16) {
-    if (pos0 + 16 < S) load_kv(pos0 + 16, okn, kn8, vn8);
-    else okn = false;
-    bool ok = okc;
-    float sc = 0.f;
-    if (ok) {
-#pragma unroll
-      for (int i = 0; i < E; ++i) sc += qv[i] * bf2f(kc8[i]);
-    }
-    // reduce over the 16-lane group
-    sc = group16_reduce(sc, SumOp());
-    sc = ok ? sc * scale : -1e30f;
-    // online softmax across the 4 position-slots handled by this wave-step
-    float m_new = fmaxf(m, sc);
-    float corr = __expf(m - m_new);       // underflows to 0 for the sentinel
-    float p = ok ? __expf(sc - m_new) : 0.f;
-    l = l * corr + p;
-    m = m_new;
-#pragma unroll
-    for (int i = 0; i < E; ++i) {
-      float vvf = ok ? bf2f(vc8[i]) : 0.f;
-      oacc[i] = oacc[i] * corr + p * vvf;
-    }
-    okc = okn; kc8 = kn8; vc8 = vn8;
-  }
-
-  // ---- merge the 16 position-slot partials (4 waves x 4 slots) ----------
-  // each (wid, lp) slot has (m, l, oacc[8]) per l16 group
-  __shared__ float sm[16], sl[16];
-  __shared__ float so[16][D];
-  const int slot_id = wid * 4 + lp;
-  if (l16 == 0) {
-    sm[slot_id] = m;
-    sl[slot_id] = l;
-  }
-#pragma unroll
-  for (int i = 0; i < E; ++i) so[slot_id][l16 * E + i] = oacc[i];
-  __syncthreads();
-  if (tid < 64) {
-    // wave 0 merges 16 slots
-    float gm = -1e30f;
-#pragma unroll
-    for (int s2 = 0; s2 < 16; ++s2) gm = fmaxf(gm, sm[s2]);
-    float gl = 0.f;
-    float out[E];
-#pragma unroll
-    for (int i = 0; i < E; ++i) out[i] = 0.f;
-#pragma unroll
-    for (int s2 = 0; s2 < 16; ++s2) {
-      float w = (sl[s2] > 0.f) ? __expf(sm[s2] - gm) : 0.f;
-      gl += sl[s2] * w;
-#pragma unroll
-      for (int i = 0; i < E; ++i) out[i] += w * so[s2][l16 * E + i];
-    }
-    if (lane < 16) {
-      float inv = gl > 0.f ? 1.f / gl : 0.f;
-      short* op = og + ((long long)b * H + h) * D;
-#pragma unroll
-      for (int i = 0; i < E; ++i) op[l16 * E + i] = f2bf(out[i] * inv);
-    }
-  }
-}
-
-void decode_attention(const void* q, const void* kcache, const void* vcache,
-                      const int* block_table, const int* seq_lens, void* o,
-                      int64_t b, int64_t h, int64_t hkv, int64_t bs,
-                      int64_t max_blocks, int64_t dh, float scale,
-                      int64_t blk_str, int64_t pos_str, int64_t head_str,
-                      hipStream_t s) {
-  dim3 grid((unsigned)(b * h));
-  if (blk_str == 0) {   // default paged layout [nblocks, bs, HKV, D]
-    blk_str = bs * hkv * dh;
-    pos_str = hkv * dh;
-    head_str = dh;
-  }
-  if (dh == 128)
-    hipLaunchKernelGGL((decode_attn_kernel<128>), grid, dim3(256), 0, s,
-                       (const short*)q, (const short*)kcache, (const short*)vcache,
-                       block_table, seq_lens, (short*)o, (int)b, (int)h,
-                       (int)hkv, (int)bs, (int)max_blocks, scale,
-                       blk_str, pos_str, head_str);
-  else
-    hipLaunchKernelGGL((decode_attn_kernel<64>), grid, dim3(256), 0, s,
-                       (const short*)q, (const short*)kcache, (const short*)vcache,
-                       block_table, seq_lens, (short*)o, (int)b, (int)h,
-                       (int)hkv, (int)bs, (int)max_blocks, scale,
-                       blk_str, pos_str, head_str);
-}
 
 // ===========================================================================
 // int8 paged KV cache (docs/KERNELS.md "int8 KV cache")
@@ -279,162 +141,317 @@ void kv_quant_append(const void* k, const void* v, void* kcache, void* vcache,
 #undef PA_KVQ_LAUNCH
 }
 
-// int8 sibling of decode_attn_kernel: same decomposition (one 256-thread
-// block per (b, q-head), online softmax, pipelined next-step loads, LDS slot
-// merge by wave 0) with 16 codes = 16 B per lane in flight:
-//   D/16 lanes per position (8 | 4), 64/(D/16) positions per wave step,
-//   SLOTS = 4x that (32 | 64) merge slots, so[SLOTS][D] fp32 = 16 KB.
-// Scales act on the result, not on the element: the softmax scale is folded
-// into q, score = (sum q_i code_i) * d_k[pos], oacc += (p * d_v[pos]) * code.
-// d_k / d_v load in the same prefetch stage as the codes.
-template <int D>
+// ===========================================================================
+// decode attention
+// ===========================================================================
+// int8 scales act on the result, not on the element: the softmax scale is
+// folded into q, score = (sum q_i code_i) * d_k[pos],
+// oacc += (p * d_v[pos]) * code.
+template <int D, int GT, bool INT8, bool PARTIAL>
 __launch_bounds__(256)
-__global__ void decode_attn_int8_kernel(
-    const short* __restrict__ qg, const signed char* __restrict__ kcache,
-    const signed char* __restrict__ vcache, const float* __restrict__ kscale,
-    const float* __restrict__ vscale, const int* __restrict__ block_table,
-    const int* __restrict__ seq_lens, short* __restrict__ og, int H, int HKV,
-    int bs, int max_blocks, int nblocks, float scale, long long ss_blk,
-    long long ss_pos, long long ss_head) {
-  constexpr int LPP = D / 16;            // lanes per position
-  constexpr int PPW = 64 / LPP;          // positions per wave step
-  constexpr int SLOTS = 4 * PPW;         // positions per block step
-  const int b = blockIdx.x / H;
-  const int h = blockIdx.x % H;
-  const int hkv = h / (H / HKV);
+__global__ void decode_attn_kernel(const DecodeAttnArgs a, const int tiles) {
+  constexpr int E = INT8 ? 16 : D / 16;     // elements per lane
+  constexpr int LPP = D / E;                // lanes per position
+  constexpr int PPW = 64 / LPP;             // positions per wave step
+  constexpr int SLOTS = 4 * PPW;            // positions per block step
+  static_assert(64 % SLOTS == 0, "slice granule 64 covers whole block steps");
+  using cache_t = std::conditional_t<INT8, signed char, short>;
+  const cache_t* __restrict__ kcache = (const cache_t*)a.kcache;
+  const cache_t* __restrict__ vcache = (const cache_t*)a.vcache;
+  const int* __restrict__ block_table = a.block_table;
+  const int H = a.h, HKV = a.hkv, bs = a.bs, max_blocks = a.max_blocks;
+  const int nsplit = PARTIAL ? a.nsplit : 1;
+
+  int idx = blockIdx.x;
+  const int s = idx % nsplit; idx /= nsplit;
+  const int tile = idx % tiles; idx /= tiles;
+  const int hkv = idx % HKV;
+  const int b = idx / HKV;
+  const int G = H / HKV;
+  const int h0 = hkv * G + tile * GT;       // first q-head of the tile
+  const int nh = min(GT, G - tile * GT);    // live heads; surplus is guarded
+
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wid = tid >> 6;
-  const int lg = lane % LPP;             // 16-element group within D
-  const int lp = lane / LPP;             // position slot within the wave
-  // never walk past the table: entries beyond ceil(S/bs) are not read
-  const int S = min(seq_lens[b], max_blocks * bs);
+  const int lg = lane % LPP;                // element group within D
+  const int lp = lane / LPP;                // position slot within the wave
 
-  float qv[16];
-  {
-    const short* qp = qg + ((long long)b * H + h) * D + lg * 16;
-    const shortx8 q0 = *reinterpret_cast<const shortx8*>(qp);
-    const shortx8 q1 = *reinterpret_cast<const shortx8*>(qp + 8);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      qv[i] = bf2f(q0[i]) * scale;
-      qv[8 + i] = bf2f(q1[i]) * scale;
-    }
+  // never walk past the table; PARTIAL: the slice rule (part of the contract)
+  const int S = max(0, min(a.seq_lens[b], max_blocks * bs));
+  int begin = 0, end = S;
+  if constexpr (PARTIAL) {
+    const int c = 64 * ((S + 64 * nsplit - 1) / (64 * nsplit));
+    begin = s * c;
+    end = min(S, begin + c);
   }
 
-  float m = -1e30f, l = 0.f;  // finite sentinel: -ffast-math breaks +-inf
-  float oacc[16];
-#pragma unroll
-  for (int i = 0; i < 16; ++i) oacc[i] = 0.f;
+  // Result of head g of the tile, called by the thread tid < D that owns
+  // column tid: the partial (out, gm, gl), or the normalised bf16 output.
+  const long long row0 = ((long long)b * H + h0) * nsplit + s;  // + g * nsplit
+  auto store = [&](int g, float out, float gm, float gl) {
+    const long long r = row0 + (long long)g * nsplit;
+    if constexpr (PARTIAL) {
+      a.o_part[r * D + tid] = out;
+      if (tid == 0)
+        *reinterpret_cast<float2*>(a.ml_part + r * 2) = make_float2(gm, gl);
+    } else {
+      ((short*)a.o)[r * D + tid] = f2bf(out * (gl > 0.f ? 1.f / gl : 0.f));
+    }
+  };
+  if (begin >= end) {                       // nothing to read: l = 0, m = -1e30
+    if (tid < D)
+      for (int g = 0; g < nh; ++g) store(g, 0.f, -1e30f, 0.f);
+    return;
+  }
 
+  // One position's K and V for this lane: 16 B each (8 B at bf16 D = 64),
+  // plus d_k / d_v of the int8 cache in the same prefetch stage.
   auto load_kv = [&](int pos0, bool& ok, uint4& kw, uint4& vw, float& dk,
                      float& dv) {
     const int pos = pos0 + lp;
-    ok = pos < S;
+    ok = pos < end;
     if (ok) {
       const int phys = block_table[(long long)b * max_blocks + pos / bs];
       const int off = pos % bs;
       // a table entry outside the pool reads nothing (wrong numbers, no fault)
-      ok = (unsigned)phys < (unsigned)nblocks;
+      ok = (unsigned)phys < (unsigned)a.nblocks;
       if (ok) {
-        const long long row = ((long long)phys * bs + off) * HKV + hkv;
-        const long long srow = (long long)phys * ss_blk +
-                               (long long)off * ss_pos +
-                               (long long)hkv * ss_head;
-        kw = *reinterpret_cast<const uint4*>(kcache + row * D + lg * 16);
-        vw = *reinterpret_cast<const uint4*>(vcache + row * D + lg * 16);
-        dk = kscale[srow];
-        dv = vscale[srow];
+        const long long row = (long long)phys * a.cs_blk +
+                              (long long)off * a.cs_pos +
+                              (long long)hkv * a.cs_head + lg * E;
+        if constexpr (E == 4) {
+          const uint2 k2 = *reinterpret_cast<const uint2*>(kcache + row);
+          const uint2 v2 = *reinterpret_cast<const uint2*>(vcache + row);
+          kw.x = k2.x; kw.y = k2.y;
+          vw.x = v2.x; vw.y = v2.y;
+        } else {
+          kw = *reinterpret_cast<const uint4*>(kcache + row);
+          vw = *reinterpret_cast<const uint4*>(vcache + row);
+        }
+        if constexpr (INT8) {
+          const long long srow = (long long)phys * a.ss_blk +
+                                 (long long)off * a.ss_pos +
+                                 (long long)hkv * a.ss_head;
+          dk = a.kscale[srow];
+          dv = a.vscale[srow];
+        }
       }
+    }
+  };
+  // element i of a loaded register quad as float
+  auto elem = [](const unsigned (&w)[4], int i) -> float {
+    if constexpr (INT8) {
+      return code2f(w[i >> 2], i & 3);
+    } else {
+      const unsigned u = w[i >> 1];
+      return __uint_as_float((i & 1) ? (u & 0xffff0000u) : (u << 16));
     }
   };
 
   bool okc = false, okn = false;
   uint4 kc = make_uint4(0, 0, 0, 0), vc = kc, kn = kc, vn = kc;
-  float dkc = 0.f, dvc = 0.f, dkn = 0.f, dvn = 0.f;
-  const int p_start = wid * PPW;
+  float dkc = 1.f, dvc = 1.f, dkn = 1.f, dvn = 1.f;
+  const int p_start = begin + wid * PPW;
   load_kv(p_start, okc, kc, vc, dkc, dvc);
-  for (int pos0 = p_start; pos0 < S; pos0 += SLOTS) {
-    if (pos0 + SLOTS < S) load_kv(pos0 + SLOTS, okn, kn, vn, dkn, dvn);
+
+  // q of the tile's heads, softmax scale folded in; a surplus head is zero
+  // and its q is never read.  Loaded after the first K/V so that the two
+  // latencies overlap.
+  float qv[GT][E];
+#pragma unroll
+  for (int g = 0; g < GT; ++g) {
+#pragma unroll
+    for (int i = 0; i < E; ++i) qv[g][i] = 0.f;
+    if (g < nh) {
+      const short* qp =
+          (const short*)a.q + ((long long)b * H + h0 + g) * D + lg * E;
+      if constexpr (E == 4) {
+        const shortx4 q4 = *reinterpret_cast<const shortx4*>(qp);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) qv[g][i] = bf2f(q4[i]) * a.scale;
+      } else {
+#pragma unroll
+        for (int j = 0; j < E; j += 8) {
+          const shortx8 q8 = *reinterpret_cast<const shortx8*>(qp + j);
+#pragma unroll
+          for (int i = 0; i < 8; ++i) qv[g][j + i] = bf2f(q8[i]) * a.scale;
+        }
+      }
+    }
+  }
+
+  float m[GT], l[GT], oacc[GT][E];
+#pragma unroll
+  for (int g = 0; g < GT; ++g) {
+    m[g] = -1e30f;  // finite sentinel: -ffast-math breaks +-inf
+    l[g] = 0.f;
+#pragma unroll
+    for (int i = 0; i < E; ++i) oacc[g][i] = 0.f;
+  }
+
+  // s_waitcnt vmcnt(0): the first loads land before the loop.  Left pending
+  // across the loop header, they make the compiler wait inside every step
+  // right after the prefetch is issued (for the prefetch's own first load),
+  // which serialises load latency and math; with this the step waits only
+  // where it rotates the registers, at its end.
+  __builtin_amdgcn_s_waitcnt(0x0F70);
+  for (int pos0 = p_start; pos0 < end; pos0 += SLOTS) {
+    if (pos0 + SLOTS < end) load_kv(pos0 + SLOTS, okn, kn, vn, dkn, dvn);
     else okn = false;
     const bool ok = okc;
     const unsigned kwd[4] = {kc.x, kc.y, kc.z, kc.w};
-    const unsigned vwd[4] = {vc.x, vc.y, vc.z, vc.w};
-    float sc = 0.f;
+    // p = 0 masks a position: enough for codes, which are finite; stale bf16
+    // bits are zeroed a word at a time
+    const bool vlive = INT8 || ok;
+    const unsigned vwd[4] = {vlive ? vc.x : 0u, vlive ? vc.y : 0u,
+                             vlive ? vc.z : 0u, vlive ? vc.w : 0u};
+    // K of this position, decoded once for the GT heads
+    float kf[E];
 #pragma unroll
-    for (int i = 0; i < 16; ++i) sc += qv[i] * code2f(kwd[i >> 2], i & 3);
-    sc = group_reduce<LPP>(sc, SumOp());
-    sc = ok ? sc * dkc : -1e30f;
-    const float m_new = fmaxf(m, sc);
-    const float corr = __expf(m - m_new);  // underflows to 0 for the sentinel
-    const float p = ok ? __expf(sc - m_new) : 0.f;
-    l = l * corr + p;
-    m = m_new;
-    const float pv = ok ? p * dvc : 0.f;
+    for (int i = 0; i < E; ++i) kf[i] = elem(kwd, i);
+    float p[GT], corr[GT];
 #pragma unroll
-    for (int i = 0; i < 16; ++i)
-      oacc[i] = oacc[i] * corr + pv * code2f(vwd[i >> 2], i & 3);
+    for (int g = 0; g < GT; ++g) {
+      float sc = 0.f;
+#pragma unroll
+      for (int i = 0; i < E; ++i) sc += qv[g][i] * kf[i];
+      sc = group_reduce<LPP>(sc, SumOp());
+      if constexpr (INT8) sc *= dkc;
+      sc = ok ? sc : -1e30f;
+      const float m_new = fmaxf(m[g], sc);
+      corr[g] = __expf(m[g] - m_new);     // underflows to 0 for the sentinel
+      const float pg = ok ? __expf(sc - m_new) : 0.f;
+      l[g] = l[g] * corr[g] + pg;
+      m[g] = m_new;
+      if constexpr (INT8) p[g] = ok ? pg * dvc : 0.f;
+      else p[g] = pg;
+    }
+#pragma unroll
+    for (int i = 0; i < E; ++i) {
+      const float vf = elem(vwd, i);
+#pragma unroll
+      for (int g = 0; g < GT; ++g)
+        oacc[g][i] = oacc[g][i] * corr[g] + p[g] * vf;
+    }
     okc = okn; kc = kn; vc = vn; dkc = dkn; dvc = dvn;
   }
 
-  // ---- merge the SLOTS position-slot partials (4 waves x PPW slots) -------
+  // ---- in-block merge of the SLOTS position-slot partials, head by head ---
+  // One LDS image reused for every head of the tile; thread `tid < D` owns
+  // one output column and walks the slots in fixed order.
   __shared__ float sm[SLOTS], sl[SLOTS];
   __shared__ __attribute__((aligned(16))) float so[SLOTS][D];
   const int slot_id = wid * PPW + lp;
-  if (lg == 0) {
-    sm[slot_id] = m;
-    sl[slot_id] = l;
-  }
 #pragma unroll
-  for (int i = 0; i < 16; i += 4) {
-    floatx4 o4 = {oacc[i], oacc[i + 1], oacc[i + 2], oacc[i + 3]};
-    *reinterpret_cast<floatx4*>(&so[slot_id][lg * 16 + i]) = o4;
-  }
-  __syncthreads();
-  if (tid < 64) {
-    // wave 0: lane owns D/64 output elements across all slots
-    constexpr int EPL = D / 64;
-    float gm = -1e30f;
-#pragma unroll
-    for (int s2 = 0; s2 < SLOTS; ++s2) gm = fmaxf(gm, sm[s2]);
-    float gl = 0.f;
-    float out[EPL];
-#pragma unroll
-    for (int i = 0; i < EPL; ++i) out[i] = 0.f;
-#pragma unroll 8
-    for (int s2 = 0; s2 < SLOTS; ++s2) {
-      const float w = (sl[s2] > 0.f) ? __expf(sm[s2] - gm) : 0.f;
-      gl += sl[s2] * w;
-#pragma unroll
-      for (int i = 0; i < EPL; ++i) out[i] += w * so[s2][lane * EPL + i];
+  for (int g = 0; g < GT; ++g) {
+    if (g >= nh) break;                     // block-uniform
+    if (g > 0) __syncthreads();             // readers of the previous head
+    if (lg == 0) {
+      sm[slot_id] = m[g];
+      sl[slot_id] = l[g];
     }
-    const float inv = gl > 0.f ? 1.f / gl : 0.f;   // S == 0 -> zeros
-    short* op = og + ((long long)b * H + h) * D + lane * EPL;
 #pragma unroll
-    for (int i = 0; i < EPL; ++i) op[i] = f2bf(out[i] * inv);
+    for (int i = 0; i < E; i += 4) {
+      const floatx4 o4 = {oacc[g][i], oacc[g][i + 1], oacc[g][i + 2],
+                          oacc[g][i + 3]};
+      *reinterpret_cast<floatx4*>(&so[slot_id][lg * E + i]) = o4;
+    }
+    __syncthreads();
+    if (tid < D) {
+      float gm = -1e30f;
+#pragma unroll
+      for (int s2 = 0; s2 < SLOTS; ++s2) gm = fmaxf(gm, sm[s2]);
+      float gl = 0.f, out = 0.f;
+#pragma unroll 8
+      for (int s2 = 0; s2 < SLOTS; ++s2) {
+        const float w = (sl[s2] > 0.f) ? __expf(sm[s2] - gm) : 0.f;
+        gl += sl[s2] * w;
+        out += w * so[s2][tid];
+      }
+      store(g, out, gm, gl);
+    }
   }
 }
 
-void decode_attention_int8(const void* q, const void* kcache,
-                           const void* vcache, const float* kscale,
-                           const float* vscale, const int* block_table,
-                           const int* seq_lens, void* o, int64_t b, int64_t h,
-                           int64_t hkv, int64_t bs, int64_t max_blocks,
-                           int64_t nblocks, int64_t dh, float scale,
-                           int64_t ss_blk, int64_t ss_pos, int64_t ss_head,
-                           hipStream_t s) {
-  if (b * h == 0) return;
-  dim3 grid((unsigned)(b * h));
-#define PA_DA8_LAUNCH(DH)                                                     \
-  hipLaunchKernelGGL((decode_attn_int8_kernel<DH>), grid, dim3(256), 0, s,    \
-                     (const short*)q, (const signed char*)kcache,             \
-                     (const signed char*)vcache, kscale, vscale, block_table, \
-                     seq_lens, (short*)o, (int)h, (int)hkv, (int)bs,          \
-                     (int)max_blocks, (int)nblocks, scale,                    \
-                     (long long)ss_blk, (long long)ss_pos, (long long)ss_head)
-  if (dh == 128) PA_DA8_LAUNCH(128);
-  else PA_DA8_LAUNCH(64);
-#undef PA_DA8_LAUNCH
+// One wave per (b, h) row, 4 rows per block; lane owns D/64 output elements.
+// Splits combine in index order: gm = max m_s, w_s = l_s > 0 ? exp(m_s - gm)
+// : 0, out = sum w_s o_s / sum w_s l_s.  A row with no live split is zero.
+template <int D>
+__launch_bounds__(256)
+__global__ void decode_attn_merge_kernel(const float* __restrict__ o_part,
+                                         const float* __restrict__ ml_part,
+                                         short* __restrict__ og,
+                                         long long rows, int nsplit) {
+  constexpr int EPL = D / 64;
+  const int lane = threadIdx.x & 63;
+  const long long r = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= rows) return;                    // whole waves leave together
+  const float* ml = ml_part + r * nsplit * 2;
+  const float* op = o_part + r * nsplit * D + lane * EPL;
+  float gm = -1e30f;
+  for (int s = 0; s < nsplit; ++s) gm = fmaxf(gm, ml[2 * s]);
+  float gl = 0.f, out[EPL];
+#pragma unroll
+  for (int i = 0; i < EPL; ++i) out[i] = 0.f;
+  for (int s = 0; s < nsplit; ++s) {
+    const float ls = ml[2 * s + 1];
+    const float w = ls > 0.f ? __expf(ml[2 * s] - gm) : 0.f;
+    gl += w * ls;
+#pragma unroll
+    for (int i = 0; i < EPL; ++i) out[i] += w * op[(long long)s * D + i];
+  }
+  const float inv = gl > 0.f ? 1.f / gl : 0.f;   // S == 0 -> zeros
+#pragma unroll
+  for (int i = 0; i < EPL; ++i) og[r * D + lane * EPL + i] = f2bf(out[i] * inv);
+}
+
+DecodeAttnSplitPlan decode_attn_split_plan(int64_t b, int64_t h, int64_t hkv,
+                                           int64_t nsplit, bool int8) {
+  const int64_t g = hkv > 0 ? h / hkv : 1;
+  const int gmax = int8 ? 4 : 8;
+  int gt = 1;
+  while (gt < g && gt < gmax) gt *= 2;
+  const int tiles = (int)((g + gt - 1) / gt);
+  return {gt, tiles, b * hkv * tiles * nsplit};
+}
+
+void decode_attention(const DecodeAttnArgs& a, hipStream_t s) {
+  if ((int64_t)a.b * a.h == 0) return;
+  const bool int8 = a.kscale != nullptr, partial = a.nsplit > 0;
+  const DecodeAttnSplitPlan plan =
+      partial ? decode_attn_split_plan(a.b, a.h, a.hkv, a.nsplit, int8)
+              : DecodeAttnSplitPlan{1, a.h / a.hkv, (int64_t)a.b * a.h};
+  const dim3 grid((unsigned)plan.blocks);
+#define PA_DA_LAUNCH(DH, GT, I8, P)                                           \
+  hipLaunchKernelGGL((decode_attn_kernel<DH, GT, I8, P>), grid, dim3(256), 0, \
+                     s, a, plan.tiles)
+  // unsplit: GT = 1; GT = 8 exists for the bf16 cache only (the plan never
+  // asks int8 for it)
+#define PA_DA_GT(DH, I8, GTMAX)                                               \
+  if (!partial) PA_DA_LAUNCH(DH, 1, I8, false);                               \
+  else switch (plan.gt) {                                                     \
+    case 1: PA_DA_LAUNCH(DH, 1, I8, true); break;                             \
+    case 2: PA_DA_LAUNCH(DH, 2, I8, true); break;                             \
+    case 4: PA_DA_LAUNCH(DH, 4, I8, true); break;                             \
+    default: PA_DA_LAUNCH(DH, GTMAX, I8, true); break;                        \
+  }
+  if (int8) {
+    if (a.dh == 128) { PA_DA_GT(128, true, 4) } else { PA_DA_GT(64, true, 4) }
+  } else {
+    if (a.dh == 128) { PA_DA_GT(128, false, 8) } else { PA_DA_GT(64, false, 8) }
+  }
+#undef PA_DA_GT
+#undef PA_DA_LAUNCH
+  if (!partial) return;
+  const long long rows = (long long)a.b * a.h;
+  const dim3 mgrid((unsigned)((rows + 3) / 4));
+  if (a.dh == 128)
+    hipLaunchKernelGGL((decode_attn_merge_kernel<128>), mgrid, dim3(256), 0, s,
+                       a.o_part, a.ml_part, (short*)a.o, rows, a.nsplit);
+  else
+    hipLaunchKernelGGL((decode_attn_merge_kernel<64>), mgrid, dim3(256), 0, s,
+                       a.o_part, a.ml_part, (short*)a.o, rows, a.nsplit);
 }
 
 }  // namespace pa

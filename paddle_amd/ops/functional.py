@@ -1122,33 +1122,6 @@ def _kv_int8_pools_ok(k_cache, v_cache, k_scale, v_scale):
             or tuple(k_scale.shape) == (k_cache.shape[2],))
 
 
-def _kv_int8_native_ok(q, k_cache, v_cache, k_scale, v_scale, block_table,
-                       seq_lens):
-    """Contract of decode_attention_int8 (pure: dtypes, shapes, strides,
-    devices).  q bf16 [B, H, D] (the dispatch site passes it contiguous),
-    D in {64, 128} equal to the cache's, H % HKV == 0; pools per
-    _kv_int8_pools_ok; block_table [B, max_blocks] and seq_lens [B]
-    integer tensors (the site casts them to int32)."""
-    if not (isinstance(q, torch.Tensor) and q.dtype == torch.bfloat16
-            and q.dim() == 3 and _kv_int8_pools_ok(k_cache, v_cache, k_scale,
-                                                   v_scale)):
-        return False
-    b, h, d = q.shape
-    if d not in (64, 128) or d != k_cache.shape[3] or h == 0 \
-            or h % k_cache.shape[2]:
-        return False
-    if q.is_contiguous() and (q.storage_offset() * 2) % 16:
-        return False
-    ints = (torch.int32, torch.int64)
-    if not (isinstance(block_table, torch.Tensor) and block_table.dim() == 2
-            and block_table.shape[0] == b and block_table.dtype in ints
-            and isinstance(seq_lens, torch.Tensor) and seq_lens.dim() == 1
-            and seq_lens.shape[0] == b and seq_lens.dtype in ints):
-        return False
-    return all(t.device == q.device
-               for t in (k_cache, block_table, seq_lens))
-
-
 def _kv_quant_append_native_ok(k, v, k_cache, v_cache, k_scale, v_scale, blk,
                                off, k_quant_scale=None, v_quant_scale=None):
     """Contract of kv_quant_append (pure).  k/v bf16 [T, HKV, D] views with
@@ -1276,32 +1249,36 @@ def _decode_attn_split_plan(B, H, HKV, D, capacity, int8):
     return max(int(n), 1)
 
 
-def _decode_attn_split_native_ok(q, k_cache, v_cache, block_table, seq_lens,
-                                 k_scale=None, v_scale=None):
-    """Contract of decode_attention_split (pure: dtypes, shapes, strides,
-    devices).  With scales: _kv_int8_native_ok.  Without: bf16 contiguous
-    [nblocks, bs, HKV, D] caches of equal shape on q's device, q bf16
-    [B, H, D] (the dispatch site passes it contiguous) 16-byte aligned,
-    D in {64, 128} equal to the cache's, H % HKV == 0, block_table
-    [B, max_blocks] and seq_lens [B] integer tensors (the site casts them to
-    int32)."""
+def _paged_decode_native_ok(q, k_cache, v_cache, block_table, seq_lens,
+                            k_scale=None, v_scale=None):
+    """Contract of decode_attention / decode_attention_int8 /
+    decode_attention_split for the paged layout (pure: dtypes, shapes,
+    strides, devices; mirrors check_paged_decode in csrc/bindings.cpp).
+    Everything on q's device; with scales int8 pools per _kv_int8_pools_ok,
+    without bf16 contiguous [nblocks, bs, HKV, D] caches of equal shape;
+    caches 16-byte aligned; q bf16 [B, H, D] (the dispatch site passes it
+    contiguous) 16-byte aligned, D in {64, 128} equal to the cache's,
+    H % HKV == 0; block_table [B, max_blocks] and seq_lens [B] integer
+    tensors (the site casts them to int32)."""
     if (k_scale is None) != (v_scale is None):
         return False
-    if k_scale is not None:
-        return _kv_int8_native_ok(q, k_cache, v_cache, k_scale, v_scale,
-                                  block_table, seq_lens)
     ts = (q, k_cache, v_cache, block_table, seq_lens)
     if not all(isinstance(t, torch.Tensor) for t in ts):
         return False
     if any(t.device != q.device for t in ts):
         return False
-    if not (q.dtype == torch.bfloat16 and q.dim() == 3
-            and k_cache.dtype == torch.bfloat16
-            and v_cache.dtype == torch.bfloat16 and k_cache.dim() == 4
-            and k_cache.shape == v_cache.shape and k_cache.is_contiguous()
-            and v_cache.is_contiguous() and k_cache.numel() > 0
-            and (k_cache.storage_offset() * 2) % 16 == 0
-            and (v_cache.storage_offset() * 2) % 16 == 0):
+    if k_scale is not None:
+        if not (_kv_int8_pools_ok(k_cache, v_cache, k_scale, v_scale)):
+            return False
+    elif not (k_cache.dtype == torch.bfloat16
+              and v_cache.dtype == torch.bfloat16 and k_cache.dim() == 4
+              and k_cache.shape == v_cache.shape and k_cache.is_contiguous()
+              and v_cache.is_contiguous() and k_cache.numel() > 0):
+        return False
+    if any((t.storage_offset() * t.element_size()) % 16
+           for t in (k_cache, v_cache)):
+        return False
+    if not (q.dtype == torch.bfloat16 and q.dim() == 3):
         return False
     b, h, d = q.shape
     if d not in (64, 128) or d != k_cache.shape[3] or h == 0 \
@@ -1315,6 +1292,16 @@ def _decode_attn_split_native_ok(q, k_cache, v_cache, block_table, seq_lens,
             and seq_lens.shape[0] == b and seq_lens.dtype in ints)
 
 
+# the names the int8 and split-KV predicates had before they became one
+_decode_attn_split_native_ok = _paged_decode_native_ok
+
+
+def _kv_int8_native_ok(q, k_cache, v_cache, k_scale, v_scale, block_table,
+                       seq_lens):
+    return k_scale is not None and _paged_decode_native_ok(
+        q, k_cache, v_cache, block_table, seq_lens, k_scale, v_scale)
+
+
 def paged_decode_attention(q, k_cache, v_cache, block_table, seq_lens, scale=None,
                            k_scale=None, v_scale=None, num_splits=None):
     """One decode step. q: [B, H, D]; k/v_cache: [nblocks, block_size, HKV, D];
@@ -1322,12 +1309,12 @@ def paged_decode_attention(q, k_cache, v_cache, block_table, seq_lens, scale=Non
     With k_scale/v_scale the caches are int8 code pools (docs/KERNELS.md
     "int8 KV cache"): fp32 scales [nblocks, block_size, HKV] (per token, as
     kv_cache_quant_append writes them) or [HKV] (per head).
-    num_splits chooses the kernels (docs/KERNELS.md "split-KV decode
+    num_splits chooses the launch (docs/KERNELS.md "split-KV decode
     attention"): None asks _decode_attn_split_plan, whose answer 1 means
-    the one-block-per-q-head kernels; 0 pins those kernels; n >= 1 forces
-    the split-KV kernels with n splits (n = 1: group sharing alone).
-    Outside the split kernels' contract, on CPU or with native kernels off,
-    num_splits is ignored."""
+    one block per q-head; 0 pins that; n >= 1 forces split-KV with n splits
+    (n = 1: group sharing alone).
+    Outside _paged_decode_native_ok, on CPU or with native kernels off, the
+    torch path below answers and num_splits is ignored."""
     if scale is None:
         scale = 1.0 / math.sqrt(q.shape[-1])
     int8 = k_scale is not None or v_scale is not None
@@ -1337,20 +1324,6 @@ def paged_decode_attention(q, k_cache, v_cache, block_table, seq_lens, scale=Non
         raise ValueError("paged_decode_attention: num_splits must be None or "
                          f"an integer in [0, {_DECODE_ATTN_SPLIT_MAX}], got "
                          f"{num_splits!r}")
-    if num_splits != 0 and (not int8 or (k_scale is not None
-                                         and v_scale is not None)) \
-            and _ext.use_native(q) and _decode_attn_split_native_ok(
-                q, k_cache, v_cache, block_table, seq_lens, k_scale, v_scale):
-        n = num_splits
-        if n is None:
-            n = _decode_attn_split_plan(
-                q.shape[0], q.shape[1], k_cache.shape[2], q.shape[2],
-                block_table.shape[1] * k_cache.shape[1], int8)
-        if num_splits is not None or n > 1:
-            return _ext.get_ext().decode_attention_split(
-                q.contiguous(), k_cache, v_cache,
-                block_table.int().contiguous(), seq_lens.int().contiguous(),
-                scale, int(n), k_scale, v_scale)
     if int8:
         if k_scale is None or v_scale is None:
             raise ValueError("paged_decode_attention: give both k_scale and "
@@ -1360,18 +1333,24 @@ def paged_decode_attention(q, k_cache, v_cache, block_table, seq_lens, scale=Non
                 "paged_decode_attention: k_scale/v_scale need int8 contiguous "
                 "[nblocks, bs, HKV, D] caches of equal shape and fp32 "
                 "contiguous scales [nblocks, bs, HKV] or [HKV]")
-        if _ext.use_native(q) and _kv_int8_native_ok(
-                q, k_cache, v_cache, k_scale, v_scale, block_table, seq_lens):
-            C = _ext.get_ext()
-            return C.decode_attention_int8(
-                q.contiguous(), k_cache, v_cache, k_scale, v_scale,
-                block_table.int().contiguous(), seq_lens.int().contiguous(),
-                scale)
-    elif _ext.use_native(q) and q.dtype == torch.bfloat16 and q.shape[-1] in (64, 128):
+    if _ext.use_native(q) and _paged_decode_native_ok(
+            q, k_cache, v_cache, block_table, seq_lens, k_scale, v_scale):
         C = _ext.get_ext()
-        return C.decode_attention(q.contiguous(), k_cache.contiguous(),
-                                  v_cache.contiguous(), block_table.int().contiguous(),
-                                  seq_lens.int().contiguous(), scale)
+        q, table, lens = (q.contiguous(), block_table.int().contiguous(),
+                          seq_lens.int().contiguous())
+        n = num_splits
+        if n is None:
+            n = _decode_attn_split_plan(
+                q.shape[0], q.shape[1], k_cache.shape[2], q.shape[2],
+                table.shape[1] * k_cache.shape[1], int8)
+            n = n if n > 1 else 0
+        if n:
+            return C.decode_attention_split(q, k_cache, v_cache, table, lens,
+                                            scale, int(n), k_scale, v_scale)
+        if int8:
+            return C.decode_attention_int8(q, k_cache, v_cache, k_scale,
+                                           v_scale, table, lens, scale)
+        return C.decode_attention(q, k_cache, v_cache, table, lens, scale)
     # reference: gather each sequence's KV then plain attention
     B, H, D = q.shape
     HKV = k_cache.shape[2]

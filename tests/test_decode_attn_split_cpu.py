@@ -1,5 +1,5 @@
 """Split-KV paged decode attention without a GPU: a fp32 emulation of
-decode_attn_split_kernel + decode_attn_merge_kernel (slice rule, per-slot
+the split decode_attn_kernel + decode_attn_merge_kernel (slice rule, per-slot
 online softmax, in-block slot merge, partials, split merge, bf16 cast)
 showing that the bound of test_decode_attn_split_gpu.py accepts the design
 for every split count and rejects the mistakes such kernels can make; the
@@ -257,6 +257,123 @@ def test_decode_attn_split_native_ok_table():
         assert ok(*a), name
     for name, a in reject.items():
         assert not ok(*a), name
+
+
+PRED_KINDS = ("bf16", "int8_token", "int8_head")
+
+
+def _pred_args(kind):
+    """In-contract arguments of _paged_decode_native_ok, by name."""
+    c = make_case(128, 8, 2, 16, [5, 20], 2)
+    if kind == "bf16":
+        c = bf16_image(c)
+    elif kind == "int8_head":
+        c["ks"], c["vs"] = torch.ones(2), torch.ones(2)
+    return {k: c[k] for k in ("q", "kc", "vc", "table", "lens", "ks", "vs")}
+
+
+def _pred(a):
+    return hot._paged_decode_native_ok(a["q"], a["kc"], a["vc"], a["table"],
+                                       a["lens"], a["ks"], a["vs"])
+
+
+def _cut_d(a, d):
+    return dict(a, q=a["q"][..., :d].contiguous(),
+                kc=a["kc"][..., :d].contiguous(),
+                vc=a["vc"][..., :d].contiguous())
+
+
+def _misaligned(t):
+    return torch.zeros(t.numel() + 4, dtype=t.dtype)[4:].view_as(t)
+
+
+def _strided(t):
+    return t.transpose(0, 1).contiguous().transpose(0, 1)
+
+
+def _d96(a):
+    z = lambda t: torch.zeros(*t.shape[:-1], 96, dtype=t.dtype)
+    return dict(a, q=z(a["q"]), kc=z(a["kc"]), vc=z(a["vc"]))
+
+
+ALL, INT8, TOKEN = PRED_KINDS, PRED_KINDS[1:], PRED_KINDS[1:2]
+# (name, kinds it applies to, mutation of the in-contract arguments)
+PRED_ACCEPT = [
+    ("base", ALL, lambda a: a),
+    ("int64 table", ALL, lambda a: dict(a, table=a["table"].long(),
+                                        lens=a["lens"].long())),
+    ("strided q", ALL, lambda a: dict(a, q=_strided(a["q"]))),
+    ("D 64", ALL, lambda a: _cut_d(a, 64)),
+]
+PRED_REJECT = [
+    ("q fp32", ALL, lambda a: dict(a, q=a["q"].float())),
+    ("q 2-D", ALL, lambda a: dict(a, q=a["q"][0])),
+    ("q misaligned", ALL, lambda a: dict(a, q=_misaligned(a["q"]))),
+    ("q a list", ALL, lambda a: dict(a, q=a["q"].tolist())),
+    ("D 32", ALL, lambda a: _cut_d(a, 32)),
+    ("D 96", ALL, _d96),
+    ("cache D", ALL, lambda a: dict(a, q=a["q"][..., :64].contiguous())),
+    ("cache fp32", ALL, lambda a: dict(a, kc=a["kc"].float(),
+                                       vc=a["vc"].float())),
+    ("cache bf16 with scales", INT8, lambda a: dict(a, kc=a["kc"].to(BF16),
+                                                    vc=a["vc"].to(BF16))),
+    ("cache int8 without scales", INT8, lambda a: dict(a, ks=None, vs=None)),
+    ("cache strided", ALL, lambda a: dict(
+        a, kc=a["kc"].transpose(1, 2).contiguous().transpose(1, 2))),
+    ("v cache strided", ALL, lambda a: dict(
+        a, vc=a["vc"].transpose(1, 2).contiguous().transpose(1, 2))),
+    ("cache shapes", ALL, lambda a: dict(a, vc=a["vc"][:-1])),
+    ("cache misaligned", ALL, lambda a: dict(a, kc=_misaligned(a["kc"]))),
+    ("cache on another device", ALL, lambda a: dict(
+        a, kc=a["kc"].to("meta"), vc=a["vc"].to("meta"))),
+    ("H % HKV", ALL, lambda a: dict(a, q=a["q"][:, :7].contiguous())),
+    ("one scale", INT8, lambda a: dict(a, vs=None)),
+    ("scale fp64", INT8, lambda a: dict(a, ks=a["ks"].double(),
+                                        vs=a["vs"].double())),
+    ("scale kinds", TOKEN, lambda a: dict(a, vs=torch.ones(2))),
+    ("scale shape", INT8, lambda a: dict(a, ks=a["ks"][:-1], vs=a["vs"][:-1])),
+    ("scale strided", TOKEN, lambda a: dict(a, ks=_strided(a["ks"]))),
+    ("scale on another device", INT8, lambda a: dict(
+        a, ks=a["ks"].to("meta"), vs=a["vs"].to("meta"))),
+    ("table rows", ALL, lambda a: dict(a, table=a["table"][:1])),
+    ("table float", ALL, lambda a: dict(a, table=a["table"].float())),
+    ("table on another device", ALL, lambda a: dict(
+        a, table=a["table"].to("meta"))),
+    ("lens length", ALL, lambda a: dict(a, lens=a["lens"][:1])),
+    ("lens a list", ALL, lambda a: dict(a, lens=[5, 20])),
+]
+
+
+@pytest.mark.parametrize("kind", PRED_KINDS)
+def test_paged_decode_native_ok_table(kind):
+    """One predicate for decode_attention, decode_attention_int8 and
+    decode_attention_split, mirroring check_paged_decode."""
+    base = _pred_args(kind)
+    for name, kinds, mutate in PRED_ACCEPT:
+        if kind in kinds:
+            assert _pred(mutate(base)), name
+    for name, kinds, mutate in PRED_REJECT:
+        if kind in kinds:
+            assert not _pred(mutate(base)), name
+
+
+def test_paged_decode_attention_off_contract_bf16_torch_path_on_cpu():
+    """bf16 inputs outside the predicate (which the unsplit dispatch once
+    copied with .contiguous()) give what the in-contract call gives."""
+    a = _pred_args("bf16")
+    call = lambda a: hot.paged_decode_attention(a["q"], a["kc"], a["vc"],
+                                                a["table"], a["lens"])
+    base = call(a)
+    off = {
+        "cache strided": dict(
+            a, kc=a["kc"].transpose(1, 2).contiguous().transpose(1, 2),
+            vc=a["vc"].transpose(1, 2).contiguous().transpose(1, 2)),
+        "q misaligned": dict(a, q=_misaligned(a["q"]).copy_(a["q"])),
+        "cache misaligned": dict(a, kc=_misaligned(a["kc"]).copy_(a["kc"])),
+    }
+    for name, b in off.items():
+        assert not _pred(b), name
+        assert torch.equal(call(b), base), name
 
 
 # ---------------------------------------------------------------------------

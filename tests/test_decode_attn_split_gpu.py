@@ -1,4 +1,4 @@
-"""Split-KV paged decode attention on the GPU: decode_attn_split_kernel +
+"""Split-KV paged decode attention on the GPU: the split decode_attn_kernel +
 decode_attn_merge_kernel behind C.decode_attention_split, the
 paged_decode_attention(num_splits=) dispatch, the binding's contract,
 hipGraph capture with lengths changing on the device, and the runners.
@@ -138,6 +138,17 @@ def run_split(C, c, n, scale=None):
                                     c["lens"], scale, n, c["ks"], c["vs"])
 
 
+def run_unsplit(C, c, scale=None):
+    """The unsplit binding of the case's cache kind."""
+    if scale is None:
+        scale = 1.0 / math.sqrt(c["q"].shape[-1])
+    if c["ks"] is None:
+        return C.decode_attention(c["q"], c["kc"], c["vc"], c["table"],
+                                  c["lens"], scale)
+    return C.decode_attention_int8(c["q"], c["kc"], c["vc"], c["ks"], c["vs"],
+                                   c["table"], c["lens"], scale)
+
+
 # ---------------------------------------------------------------------------
 # kernels
 # ---------------------------------------------------------------------------
@@ -175,7 +186,8 @@ def test_decode_attention_split_needle_gpu(kind):
 
 @pytest.mark.gpu
 def test_decode_attention_split_length_past_table_gpu():
-    """seq_lens beyond max_blocks * bs is clamped to the table's capacity."""
+    """seq_lens beyond max_blocks * bs is clamped to the table's capacity,
+    by the split and by the unsplit bindings of both caches."""
     D, H, HKV, bs = 128, 8, 2, 16
     c = make_case(D, H, HKV, bs, [80, 33], 41)
     cap = c["table"].shape[1] * bs
@@ -188,7 +200,9 @@ def test_decode_attention_split_length_past_table_gpu():
         ref, bound = ref_of(want)
         over = dict(cc, lens=torch.tensor([cap + 1, 2 ** 31 - 1],
                                           dtype=torch.int32))
-        check("clamped", run_split(C, to_dev(over, DEV), 2), ref, bound)
+        over = to_dev(over, DEV)
+        check("clamped", run_split(C, over, 2), ref, bound)
+        check("clamped, unsplit", run_unsplit(C, over), ref, bound)
 
 
 @pytest.mark.gpu

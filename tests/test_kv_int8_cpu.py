@@ -20,7 +20,7 @@ CPU = "cpu"
 
 
 # ---------------------------------------------------------------------------
-# fp32 emulation of decode_attn_int8_kernel<128>: 32 position slots, each an
+# fp32 emulation of the unsplit int8 decode_attn_kernel<128>: 32 position slots, each an
 # online softmax with the scales on the score and on p, then the slot merge
 # and the bf16 cast.  `mutant` plants one mistake.
 # ---------------------------------------------------------------------------

@@ -1,5 +1,5 @@
 """int8 paged KV cache on the GPU: the kv_quant_append kernel, the
-decode_attention_int8 kernel, the paged_decode_attention dispatch, the
+decode_attention_int8 binding, the paged_decode_attention dispatch, the
 bindings' contract, hipGraph capture and the serving runners.
 
 Reference (independent of the code under test): this file packs and unpacks
