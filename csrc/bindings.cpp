@@ -430,27 +430,57 @@ Tensor l2norm_sq(const Tensor& x) {
 }
 
 // ---- flash attention ------------------------------------------------------
-// Tensors are logical [B, H, S, D] but may be strided VIEWS (e.g. of a packed
-// [B, S, 3, H, D] qkv) as long as D is contiguous and rows are 16B-aligned.
-static void fa_strides(const Tensor& t, int64_t* out) {
-  TORCH_CHECK(t.stride(3) == 1, "flash_attn: head_dim must be contiguous");
-  out[0] = t.stride(0);  // batch
-  out[1] = t.stride(1);  // head
-  out[2] = t.stride(2);  // seq
-  TORCH_CHECK(out[2] % 8 == 0, "flash_attn: seq stride must keep 16B alignment");
+// Dense tensors are logical [B, H, S, D] but may be strided VIEWS (e.g. of a
+// packed [B, S, 3, H, D] qkv) as long as D is contiguous and rows are
+// 16B-aligned.  Every check runs before anything is launched.
+static pa::FaStride fa_view(const Tensor& t, const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == torch::kBFloat16 && t.dim() == 4,
+              "flash_attn: ", name, " must be a bf16 GPU tensor [B, H, S, D]");
+  TORCH_CHECK(t.stride(3) == 1, "flash_attn: ", name, ": head_dim must be contiguous");
+  TORCH_CHECK(t.stride(2) % 8 == 0,
+              "flash_attn: ", name, ": seq stride must keep 16B alignment");
+  return {t.stride(0), t.stride(1), t.stride(2)};
 }
 
-static void fa_mask_strides(const Tensor& m, int64_t b, int64_t h, int64_t sq,
-                            int64_t skv, int64_t* ms) {
+static bool fa_same(const pa::FaStride& x, const pa::FaStride& y) {
+  return x.b == y.b && x.h == y.h && x.s == y.s;
+}
+
+static pa::FaStride fa_mask_strides(const Tensor& m, int64_t b, int64_t h,
+                                    int64_t sq, int64_t skv) {
   TORCH_CHECK(m.dim() == 4 && m.size(3) == skv && m.size(2) == sq &&
               (m.size(1) == 1 || m.size(1) == h) &&
               (m.size(0) == 1 || m.size(0) == b),
               "flash_attn mask must be [B|1, H|1, Sq, Skv]");
-  TORCH_CHECK(m.stride(3) == 1 && m.scalar_type() == torch::kBFloat16,
-              "flash_attn mask: bf16 with contiguous last dim");
-  ms[0] = m.size(0) == 1 ? 0 : m.stride(0);
-  ms[1] = m.size(1) == 1 ? 0 : m.stride(1);
-  ms[2] = m.stride(2);
+  TORCH_CHECK(m.is_cuda() && m.stride(3) == 1 && m.scalar_type() == torch::kBFloat16,
+              "flash_attn mask: bf16 on the GPU with contiguous last dim");
+  return {m.size(0) == 1 ? 0 : m.stride(0), m.size(1) == 1 ? 0 : m.stride(1),
+          m.stride(2)};
+}
+
+// what forward and backward share: q / k / v, the mask and the scalars
+static pa::FaArgs fa_dense_args(const Tensor& q, const Tensor& k, const Tensor& v,
+                                double scale, bool causal,
+                                const c10::optional<Tensor>& mask, double pdrop,
+                                int64_t seed, int64_t offset) {
+  pa::FaArgs a{};
+  a.q_s = fa_view(q, "q");
+  a.k_s = fa_view(k, "k");
+  TORCH_CHECK(fa_same(a.k_s, fa_view(v, "v")), "flash_attn: k/v must share strides");
+  a.b = (int)q.size(0); a.h = (int)q.size(1); a.sq = (int)q.size(2); a.dh = (int)q.size(3);
+  a.hkv = (int)k.size(1); a.skv = (int)k.size(2);
+  TORCH_CHECK(a.dh == 128 || a.dh == 64, "flash_attn: head_dim must be 64/128");
+  TORCH_CHECK(k.size(0) == a.b && k.size(3) == a.dh && v.sizes() == k.sizes(),
+              "flash_attn: k and v must be [B, HKV, Skv, D] with q's B and D");
+  TORCH_CHECK(a.hkv > 0 && a.h % a.hkv == 0, "flash_attn: H must be a multiple of HKV");
+  if (mask.has_value()) {
+    a.m_s = fa_mask_strides(*mask, a.b, a.h, a.sq, a.skv);
+    a.mask = mask->const_data_ptr();
+  }
+  a.q = q.const_data_ptr(); a.k = k.const_data_ptr(); a.v = v.const_data_ptr();
+  a.scale = (float)scale; a.causal = causal;
+  a.pdrop = (float)pdrop; a.seed = (uint64_t)seed; a.offset = (uint64_t)offset;
+  return a;
 }
 
 std::vector<Tensor> flash_attn_fwd(const Tensor& q, const Tensor& k, const Tensor& v,
@@ -458,30 +488,14 @@ std::vector<Tensor> flash_attn_fwd(const Tensor& q, const Tensor& k, const Tenso
                                    double scale, bool causal,
                                    c10::optional<Tensor> mask,
                                    double pdrop, int64_t seed, int64_t offset) {
-  TORCH_CHECK(q.is_cuda() && q.scalar_type() == torch::kBFloat16, "flash_attn: bf16 GPU only");
-  TORCH_CHECK(q.dim() == 4, "flash_attn expects [B,H,S,D]");
-  int64_t b = q.size(0), h = q.size(1), sq = q.size(2), d = q.size(3);
-  int64_t hkv = k.size(1), skv = k.size(2);
-  TORCH_CHECK(d == 128 || d == 64, "flash_attn: head_dim must be 64/128");
-  TORCH_CHECK(h % hkv == 0);
-  int64_t qs[3], ks[3], vs[3], os[3];
-  fa_strides(q, qs); fa_strides(k, ks); fa_strides(v, vs);
-  TORCH_CHECK(ks[0] == vs[0] && ks[1] == vs[1] && ks[2] == vs[2],
-              "flash_attn: k/v must share strides");
-  auto o = o_out.has_value() ? *o_out : torch::empty({b, h, sq, d}, q.options());
-  fa_strides(o, os);
-  auto lse = torch::empty({b, h, sq}, q.options().dtype(torch::kFloat));
-  int64_t ms[3] = {0, 0, 0};
-  const void* mp = nullptr;
-  if (mask.has_value()) {
-    fa_mask_strides(*mask, b, h, sq, skv, ms);
-    mp = mask->const_data_ptr();
-  }
-  pa::flash_attn_fwd32(q.const_data_ptr(), k.const_data_ptr(), v.const_data_ptr(),
-                       o.mutable_data_ptr(), lse.mutable_data_ptr<float>(), b, h,
-                       hkv, sq, skv, d, (float)scale, causal, qs, ks, os,
-                       mp, ms, (float)pdrop, (uint64_t)seed, (uint64_t)offset,
-                       cur_stream());
+  pa::FaArgs a = fa_dense_args(q, k, v, scale, causal, mask, pdrop, seed, offset);
+  auto o = o_out.has_value() ? *o_out : torch::empty({a.b, a.h, a.sq, a.dh}, q.options());
+  a.o_s = fa_view(o, "o");
+  TORCH_CHECK(o.sizes() == q.sizes(), "flash_attn: o must have q's shape");
+  auto lse = torch::empty({a.b, a.h, a.sq}, q.options().dtype(torch::kFloat));
+  a.o = o.mutable_data_ptr();
+  a.lse = lse.mutable_data_ptr<float>();
+  pa::flash_attn_fwd(a, cur_stream());
   return {o, lse};
 }
 
@@ -493,33 +507,30 @@ std::vector<Tensor> flash_attn_bwd(const Tensor& dout, const Tensor& q, const Te
                                    double scale, bool causal,
                                    c10::optional<Tensor> mask,
                                    double pdrop, int64_t seed, int64_t offset) {
-  int64_t b = q.size(0), h = q.size(1), sq = q.size(2), d = q.size(3);
-  int64_t hkv = k.size(1), skv = k.size(2);
-  TORCH_CHECK(hkv == h, "flash_attn_bwd kernel requires hkv==h (expand KV upstream)");
-  auto dq = dq_out.has_value() ? *dq_out : torch::empty({b, h, sq, d}, q.options());
-  auto dk = dk_out.has_value() ? *dk_out : torch::empty({b, hkv, skv, d}, k.options());
-  auto dv = dv_out.has_value() ? *dv_out : torch::empty({b, hkv, skv, d}, v.options());
-  auto delta = torch::empty({b, h, sq}, q.options().dtype(torch::kFloat));
-  int64_t qs[3], ks[3], vs[3], dos[3], os[3], dqs[3], dks[3], dvs[3];
-  fa_strides(q, qs); fa_strides(k, ks); fa_strides(v, vs);
-  fa_strides(dout, dos); fa_strides(o, os);
-  fa_strides(dq, dqs); fa_strides(dk, dks); fa_strides(dv, dvs);
-  TORCH_CHECK(ks[0] == vs[0] && ks[1] == vs[1] && ks[2] == vs[2]);
-  TORCH_CHECK(dks[0] == dvs[0] && dks[1] == dvs[1] && dks[2] == dvs[2],
-              "dk/dv must share strides");
-  int64_t ms[3] = {0, 0, 0};
-  const void* mp = nullptr;
-  if (mask.has_value()) {
-    fa_mask_strides(*mask, b, h, sq, skv, ms);
-    mp = mask->const_data_ptr();
-  }
-  pa::flash_attn_bwd(dout.const_data_ptr(), q.const_data_ptr(), k.const_data_ptr(),
-                     v.const_data_ptr(), o.const_data_ptr(), lse.const_data_ptr<float>(),
-                     dq.mutable_data_ptr(), dk.mutable_data_ptr(), dv.mutable_data_ptr(),
-                     delta.mutable_data_ptr<float>(), b, h, hkv, sq, skv, d,
-                     (float)scale, causal, qs, ks, dos, os, dqs, dks,
-                     mp, ms, (float)pdrop, (uint64_t)seed, (uint64_t)offset,
-                     cur_stream());
+  pa::FaArgs a = fa_dense_args(q, k, v, scale, causal, mask, pdrop, seed, offset);
+  TORCH_CHECK(a.hkv == a.h, "flash_attn_bwd kernel requires hkv==h (expand KV upstream)");
+  auto dq = dq_out.has_value() ? *dq_out : torch::empty({a.b, a.h, a.sq, a.dh}, q.options());
+  auto dk = dk_out.has_value() ? *dk_out : torch::empty({a.b, a.hkv, a.skv, a.dh}, k.options());
+  auto dv = dv_out.has_value() ? *dv_out : torch::empty({a.b, a.hkv, a.skv, a.dh}, v.options());
+  a.do_s = fa_view(dout, "dout");
+  a.o_s = fa_view(o, "o");
+  a.dq_s = fa_view(dq, "dq");
+  a.dk_s = fa_view(dk, "dk");
+  TORCH_CHECK(fa_same(a.dk_s, fa_view(dv, "dv")), "flash_attn_bwd: dk/dv must share strides");
+  TORCH_CHECK(dout.sizes() == q.sizes() && o.sizes() == q.sizes() && dq.sizes() == q.sizes(),
+              "flash_attn_bwd: dout, o and dq must have q's shape");
+  TORCH_CHECK(dk.sizes() == k.sizes() && dv.sizes() == k.sizes(),
+              "flash_attn_bwd: dk and dv must have k's shape");
+  TORCH_CHECK(lse.is_cuda() && lse.scalar_type() == torch::kFloat && lse.is_contiguous() &&
+              lse.sizes() == at::IntArrayRef({a.b, a.h, a.sq}),
+              "flash_attn_bwd: lse must be fp32 contiguous [B, H, Sq] on the GPU");
+  auto delta = torch::empty_like(lse);
+  a.dout = dout.const_data_ptr();
+  a.o = const_cast<void*>(o.const_data_ptr());
+  a.lse = const_cast<float*>(lse.const_data_ptr<float>());
+  a.delta = delta.mutable_data_ptr<float>();
+  a.dq = dq.mutable_data_ptr(); a.dk = dk.mutable_data_ptr(); a.dv = dv.mutable_data_ptr();
+  pa::flash_attn_bwd(a, cur_stream());
   return {dq, dk, dv};
 }
 
@@ -533,10 +544,9 @@ Tensor flash_attn_bwd_delta(const Tensor& dout, const Tensor& o) {
               "flash_attn_bwd_delta: dout / o must be bf16 [b, h, sq, d] GPU tensors of one shape");
   int64_t b = o.size(0), h = o.size(1), sq = o.size(2), d = o.size(3);
   TORCH_CHECK(d == 128 || d == 64, "flash_attn_bwd_delta: head_dim must be 64 or 128");
-  int64_t dos[3], os[3];
-  fa_strides(dout, dos); fa_strides(o, os);
-  for (int i = 0; i < 3; ++i)
-    TORCH_CHECK(dos[i] % 8 == 0 && os[i] % 8 == 0 && dos[i] >= 0 && os[i] >= 0,
+  const pa::FaStride dos = fa_view(dout, "dout"), os = fa_view(o, "o");
+  for (long long st : {dos.b, dos.h, dos.s, os.b, os.h, os.s})
+    TORCH_CHECK(st % 8 == 0 && st >= 0,
                 "flash_attn_bwd_delta: strides must keep rows 16-byte aligned");
   TORCH_CHECK(reinterpret_cast<uintptr_t>(dout.const_data_ptr()) % 16 == 0 &&
               reinterpret_cast<uintptr_t>(o.const_data_ptr()) % 16 == 0,
@@ -564,32 +574,70 @@ static std::pair<Tensor, int64_t> make_bmap(const Tensor& cu_cpu, int64_t blk) {
   return {t, (int64_t)map.size() / 2};
 }
 
+// Varlen: q / k / v packed [total, H, D] contiguous, cu_q / cu_k int32
+// [nseq + 1] prefix sums.  Fills the shared part of FaArgs; `keep` holds the
+// device tensors the launch reads.
+static pa::FaArgs fa_varlen_args(const Tensor& q, const Tensor& k, const Tensor& v,
+                                 const Tensor& cu_q, const Tensor& cu_k, double scale,
+                                 bool causal, double pdrop, int64_t seed, int64_t offset,
+                                 bool bwd, std::vector<Tensor>& keep) {
+  for (const Tensor* t : {&q, &k, &v})
+    TORCH_CHECK(t->is_cuda() && t->scalar_type() == torch::kBFloat16 && t->dim() == 3 &&
+                t->is_contiguous(),
+                "flash_attn_varlen: q, k, v must be contiguous bf16 GPU tensors [total, H, D]");
+  pa::FaArgs a{};
+  a.b = 1; a.h = (int)q.size(1); a.hkv = (int)k.size(1); a.dh = (int)q.size(2);
+  a.sq = (int)q.size(0); a.skv = (int)k.size(0);
+  TORCH_CHECK(a.dh == 128 || a.dh == 64, "flash_attn_varlen: head_dim must be 64/128");
+  TORCH_CHECK(k.size(2) == a.dh && v.sizes() == k.sizes(),
+              "flash_attn_varlen: k and v must be [total_k, HKV, D] with q's D");
+  TORCH_CHECK(bwd ? a.hkv == a.h : (a.hkv > 0 && a.h % a.hkv == 0),
+              bwd ? "flash_attn_varlen_bwd requires hkv == h"
+                  : "flash_attn_varlen: H must be a multiple of HKV");
+  TORCH_CHECK(cu_q.scalar_type() == torch::kInt32 && cu_k.scalar_type() == torch::kInt32 &&
+              cu_q.dim() == 1 && cu_k.dim() == 1 && cu_q.size(0) == cu_k.size(0) &&
+              cu_q.size(0) >= 2,
+              "flash_attn_varlen: cu_seqlens must be int32 [nseq + 1] of one length");
+  auto cu_q_cpu = cu_q.cpu().contiguous();
+  auto cu_k_cpu = cu_k.cpu().contiguous();
+  const int64_t n = cu_q.size(0);
+  TORCH_CHECK(cu_q_cpu.const_data_ptr<int>()[n - 1] == a.sq &&
+              cu_k_cpu.const_data_ptr<int>()[n - 1] == a.skv,
+              "flash_attn_varlen: the last cu_seqlens entries must be the packed totals");
+  keep.push_back(cu_q.is_cuda() ? cu_q.contiguous() : cu_q_cpu.cuda());
+  keep.push_back(cu_k.is_cuda() ? cu_k.contiguous() : cu_k_cpu.cuda());
+  a.cu_q = keep[0].const_data_ptr<int>();
+  a.cu_k = keep[1].const_data_ptr<int>();
+  auto [qb, nqb] = make_bmap(cu_q_cpu, 128);
+  keep.push_back(qb);
+  a.q_bmap = qb.const_data_ptr<int>(); a.n_qblocks = (int)nqb;
+  if (bwd) {
+    auto [kb, nkb] = make_bmap(cu_k_cpu, 128);
+    keep.push_back(kb);
+    a.kv_bmap = kb.const_data_ptr<int>(); a.n_kvblocks = (int)nkb;
+  }
+  const pa::FaStride qs{0, a.dh, (long long)a.h * a.dh}, ks{0, a.dh, (long long)a.hkv * a.dh};
+  a.q_s = a.o_s = a.do_s = a.dq_s = qs;
+  a.k_s = a.dk_s = ks;
+  a.q = q.const_data_ptr(); a.k = k.const_data_ptr(); a.v = v.const_data_ptr();
+  a.scale = (float)scale; a.causal = causal;
+  a.pdrop = (float)pdrop; a.seed = (uint64_t)seed; a.offset = (uint64_t)offset;
+  return a;
+}
+
 std::vector<Tensor> flash_attn_varlen_fwd(const Tensor& q, const Tensor& k,
                                           const Tensor& v, const Tensor& cu_q,
                                           const Tensor& cu_k, double scale,
                                           bool causal, double pdrop,
                                           int64_t seed, int64_t offset) {
-  TORCH_CHECK(q.is_cuda() && q.scalar_type() == torch::kBFloat16 &&
-              q.dim() == 3 && q.is_contiguous(), "varlen q: [total, H, D] bf16");
-  TORCH_CHECK(cu_q.scalar_type() == torch::kInt32 && cu_k.scalar_type() == torch::kInt32);
-  int64_t tq = q.size(0), h = q.size(1), d = q.size(2);
-  int64_t tk = k.size(0), hkv = k.size(1);
-  TORCH_CHECK(d == 128 || d == 64);
-  auto cu_q_cpu = cu_q.cpu().contiguous();
-  auto cu_k_cpu = cu_k.cpu().contiguous();
-  auto cu_q_gpu = cu_q.is_cuda() ? cu_q.contiguous() : cu_q_cpu.cuda();
-  auto cu_k_gpu = cu_k.is_cuda() ? cu_k.contiguous() : cu_k_cpu.cuda();
-  auto [bmap, nblk] = make_bmap(cu_q_cpu, 128);
+  std::vector<Tensor> keep;
+  pa::FaArgs a = fa_varlen_args(q, k, v, cu_q, cu_k, scale, causal, pdrop, seed, offset,
+                                false, keep);
   auto o = torch::empty_like(q);
-  auto lse = torch::empty({h, tq}, q.options().dtype(torch::kFloat));
-  pa::flash_attn_varlen_fwd32(q.const_data_ptr(), k.const_data_ptr(),
-                              v.const_data_ptr(), o.mutable_data_ptr(),
-                              lse.mutable_data_ptr<float>(), h, hkv, tq, tk, d,
-                              (float)scale, causal, nblk,
-                              cu_q_gpu.const_data_ptr<int>(),
-                              cu_k_gpu.const_data_ptr<int>(),
-                              bmap.const_data_ptr<int>(), (float)pdrop,
-                              (uint64_t)seed, (uint64_t)offset, cur_stream());
+  auto lse = torch::empty({a.h, a.sq}, q.options().dtype(torch::kFloat));
+  a.o = o.mutable_data_ptr();
+  a.lse = lse.mutable_data_ptr<float>();
+  pa::flash_attn_fwd(a, cur_stream());
   return {o, lse};
 }
 
@@ -600,30 +648,27 @@ std::vector<Tensor> flash_attn_varlen_bwd(const Tensor& dout, const Tensor& q,
                                           double scale, bool causal,
                                           double pdrop, int64_t seed,
                                           int64_t offset) {
-  int64_t tq = q.size(0), h = q.size(1), d = q.size(2);
-  int64_t tk = k.size(0);
-  TORCH_CHECK(k.size(1) == h, "varlen bwd requires hkv == h");
-  auto cu_q_cpu = cu_q.cpu().contiguous();
-  auto cu_k_cpu = cu_k.cpu().contiguous();
-  auto cu_q_gpu = cu_q.is_cuda() ? cu_q.contiguous() : cu_q_cpu.cuda();
-  auto cu_k_gpu = cu_k.is_cuda() ? cu_k.contiguous() : cu_k_cpu.cuda();
-  auto [qbmap, nqb] = make_bmap(cu_q_cpu, 128);
-  auto [kvbmap, nkb] = make_bmap(cu_k_cpu, 128);
+  std::vector<Tensor> keep;
+  pa::FaArgs a = fa_varlen_args(q, k, v, cu_q, cu_k, scale, causal, pdrop, seed, offset,
+                                true, keep);
+  auto doc = dout.contiguous();
+  for (const Tensor* t : std::initializer_list<const Tensor*>{&doc, &o})
+    TORCH_CHECK(t->is_cuda() && t->scalar_type() == torch::kBFloat16 && t->is_contiguous() &&
+                t->sizes() == q.sizes(),
+                "flash_attn_varlen_bwd: dout and o must be bf16 GPU tensors of q's shape, o contiguous");
+  TORCH_CHECK(lse.is_cuda() && lse.scalar_type() == torch::kFloat && lse.is_contiguous() &&
+              lse.sizes() == at::IntArrayRef({a.h, a.sq}),
+              "flash_attn_varlen_bwd: lse must be fp32 contiguous [H, total_q] on the GPU");
   auto dq = torch::empty_like(q);
   auto dk = torch::empty_like(k);
   auto dv = torch::empty_like(v);
-  auto delta = torch::empty({h, tq}, q.options().dtype(torch::kFloat));
-  pa::flash_attn_varlen_bwd(dout.contiguous().const_data_ptr(), q.const_data_ptr(),
-                            k.const_data_ptr(), v.const_data_ptr(),
-                            o.const_data_ptr(), lse.const_data_ptr<float>(),
-                            dq.mutable_data_ptr(), dk.mutable_data_ptr(),
-                            dv.mutable_data_ptr(), delta.mutable_data_ptr<float>(),
-                            h, tq, tk, d, (float)scale, causal, nqb, nkb,
-                            cu_q_gpu.const_data_ptr<int>(),
-                            cu_k_gpu.const_data_ptr<int>(),
-                            qbmap.const_data_ptr<int>(),
-                            kvbmap.const_data_ptr<int>(), (float)pdrop,
-                            (uint64_t)seed, (uint64_t)offset, cur_stream());
+  auto delta = torch::empty_like(lse);
+  a.dout = doc.const_data_ptr();
+  a.o = const_cast<void*>(o.const_data_ptr());
+  a.lse = const_cast<float*>(lse.const_data_ptr<float>());
+  a.delta = delta.mutable_data_ptr<float>();
+  a.dq = dq.mutable_data_ptr(); a.dk = dk.mutable_data_ptr(); a.dv = dv.mutable_data_ptr();
+  pa::flash_attn_bwd(a, cur_stream());
   return {dq, dk, dv};
 }
 

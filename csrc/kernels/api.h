@@ -111,54 +111,46 @@ void l2norm_sq(const void* x, float* out, int64_t numel, int dtype,
                hipStream_t s);
 
 // ---- flash attention (bf16, head_dim 128 or 64) ----------------------------
-// Logical layout [b, h, s, dh]; arbitrary (batch, head, seq) ELEMENT strides
-// per tensor (d must be innermost/contiguous, 16B-aligned rows) so packed
-// [b, s, 3, h, dh] qkv views need no transpose copies.  Strides are int64[3]
-// = {batch, head, seq}.  lse/delta fp32 [b, h, sq] contiguous.
-void flash_attn_fwd(const void* q, const void* k, const void* v, void* o,
-                    float* lse, int64_t b, int64_t h, int64_t hkv, int64_t sq,
-                    int64_t skv, int64_t dh, float scale, bool causal,
-                    const int64_t* qs, const int64_t* ks, const int64_t* os,
-                    hipStream_t s);
-// 32x32-MFMA forward variant (same contract)
-// mask: additive bf16 [B, 1|H, Sq, Skv] (ms = {m_sb, m_sh, m_sq} strides,
-// null = none); pdrop + (seed, offset): Philox attention dropout
-// (dropout_impl.cu.h:129 seed/offset semantics, recompute-deterministic)
-void flash_attn_fwd32(const void* q, const void* k, const void* v, void* o,
-                      float* lse, int64_t b, int64_t h, int64_t hkv, int64_t sq,
-                      int64_t skv, int64_t dh, float scale, bool causal,
-                      const int64_t* qs, const int64_t* ks, const int64_t* os,
-                      const void* mask, const int64_t* ms, float pdrop,
-                      uint64_t seed, uint64_t offset, hipStream_t s);
-void flash_attn_bwd_dq32(const void* dout, const void* q, const void* k,
-                         const void* v, const float* lse, const float* delta,
-                         void* dq, int64_t b, int64_t h, int64_t sq, int64_t skv,
-                         int64_t dh, float scale, bool causal,
-                         const int64_t* qs, const int64_t* ks, const int64_t* dos,
-                         const int64_t* dqs, const void* mask, const int64_t* ms,
-                         float pdrop, uint64_t seed, uint64_t offset,
-                         hipStream_t s);
-void flash_attn_bwd_dkv32(const void* dout, const void* q, const void* k,
-                          const void* v, const float* lse, const float* delta,
-                          void* dk, void* dv, int64_t b, int64_t h, int64_t sq,
-                          int64_t skv, int64_t dh, float scale, bool causal,
-                          const int64_t* qs, const int64_t* ks, const int64_t* dos,
-                          const int64_t* dks, const void* mask, const int64_t* ms,
-                          float pdrop, uint64_t seed, uint64_t offset,
-                          hipStream_t s);
-void flash_attn_bwd(const void* dout, const void* q, const void* k,
-                    const void* v, const void* o, const float* lse,
-                    void* dq, void* dk, void* dv, float* delta, int64_t b,
-                    int64_t h, int64_t hkv, int64_t sq, int64_t skv,
-                    int64_t dh, float scale, bool causal,
-                    const int64_t* qs, const int64_t* ks, const int64_t* dos,
-                    const int64_t* os, const int64_t* dqs, const int64_t* dks,
-                    const void* mask, const int64_t* ms, float pdrop,
-                    uint64_t seed, uint64_t offset, hipStream_t s);
+// Dense: logical layout [b, h, s, dh] with per-tensor (batch, head, seq)
+// ELEMENT strides (dh innermost and contiguous, 16-byte aligned rows), so
+// packed [b, s, 3, h, dh] qkv views need no transpose copies.  v shares k's
+// strides, dv shares dk's.  lse / delta fp32 [b, h, sq] contiguous.
+// mask: additive bf16 [b|1, h|1, sq, skv] by m_s (0 = broadcast), null =
+// none.  pdrop > 0 with (seed, offset): Philox attention dropout, the same
+// keep mask in forward and backward (fa_dropout_mask materialises it).
+// Varlen (cu_q != null): packed [total, h, dh] tensors, b = 1, sq / skv the
+// packed totals, strides {0, dh, h * dh}; cu_q / cu_k int32 [nseq + 1] prefix
+// sums; q_bmap / kv_bmap int32 (seq, row-within-seq) pairs, one per 128-row
+// block; lse / delta [h, total_q]; causal is bottom-right aligned; no mask.
+// The backward needs hkv == h.
+struct FaStride { long long b, h, s; };
+struct FaArgs {
+  const void *q, *k, *v;
+  void* o;              // forward: written; backward: read
+  const void* dout;
+  void *dq, *dk, *dv;
+  float* lse;           // forward: written; backward: read
+  float* delta;         // backward workspace, shaped like lse
+  const void* mask;
+  int b, h, hkv, sq, skv, dh;
+  float scale;
+  bool causal;
+  FaStride q_s, k_s, o_s, do_s, dq_s, dk_s, m_s;
+  float pdrop;
+  unsigned long long seed, offset;
+  const int *cu_q, *cu_k, *q_bmap, *kv_bmap;
+  int n_qblocks, n_kvblocks;
+};
+void flash_attn_fwd(const FaArgs& a, hipStream_t s);
+// delta = rowsum(dout * o), then dK / dV and dQ
+void flash_attn_bwd(const FaArgs& a, hipStream_t s);
 // delta[b, h, sq] = rowsum(dout * o) alone: the first kernel of the backward
 void flash_attn_bwd_delta(const void* dout, const void* o, float* delta,
                           int64_t b, int64_t h, int64_t sq, int64_t dh,
-                          const int64_t* dos, const int64_t* os, hipStream_t s);
+                          const FaStride& dos, const FaStride& os, hipStream_t s);
+// materialize the dropout keep-mask (debug/tests): out uint8 [total]
+void fa_dropout_mask(void* out, int64_t total, float p, uint64_t seed,
+                     uint64_t offset, hipStream_t s);
 
 // ---- dropout + residual add ------------------------------------------------
 // y = dropout(x, p) + residual; mask stored as uint8 per element
@@ -257,37 +249,6 @@ void gemm_bf16_ex(const void* a, const void* b, void* c, const void* bias,
 void weight_only_gemv(const void* x, const void* wq, const float* scale,
                       const void* bias, void* out, int64_t m, int64_t n,
                       int64_t k, int dtype, hipStream_t s);
-
-// varlen (flash_attn_unpadded): packed [total, H, D], ONE launch; bmap =
-// int32 (seq, offset-within-seq) pairs per block; lse/delta [H, total_q]
-void flash_attn_varlen_fwd32(const void* q, const void* k, const void* v,
-                             void* o, float* lse, int64_t h, int64_t hkv,
-                             int64_t total_q, int64_t total_k, int64_t dh,
-                             float scale, bool causal, int64_t nblocks,
-                             const int* cu_q, const int* cu_k, const int* bmap,
-                             float pdrop, uint64_t seed, uint64_t offset,
-                             hipStream_t s);
-void flash_attn_varlen_bwd32(const void* dout, const void* q, const void* k,
-                             const void* v, const float* lse, const float* delta,
-                             void* dq, void* dk, void* dv, int64_t h,
-                             int64_t total_q, int64_t total_k, int64_t dh,
-                             float scale, bool causal, int64_t nqblocks,
-                             int64_t nkvblocks, const int* cu_q, const int* cu_k,
-                             const int* qbmap, const int* kvbmap, float pdrop,
-                             uint64_t seed, uint64_t offset, hipStream_t s);
-void flash_attn_varlen_bwd(const void* dout, const void* q, const void* k,
-                           const void* v, const void* o, const float* lse,
-                           void* dq, void* dk, void* dv, float* delta,
-                           int64_t h, int64_t total_q, int64_t total_k,
-                           int64_t dh, float scale, bool causal,
-                           int64_t nqblocks, int64_t nkvblocks,
-                           const int* cu_q, const int* cu_k, const int* qbmap,
-                           const int* kvbmap, float pdrop, uint64_t seed,
-                           uint64_t offset, hipStream_t s);
-
-// materialize the dropout keep-mask (debug/tests): out uint8 [total]
-void fa_dropout_mask(void* out, int64_t total, float p, uint64_t seed,
-                     uint64_t offset, hipStream_t s);
 
 // fp8 e4m3 MX GEMM: C[m,n] (bf16) = scale_ab * (A_fp8[m,k] x Bt_fp8[n,k]^T)
 void gemm_fp8_nt(const void* a, const void* bt, void* c, const void* bias,

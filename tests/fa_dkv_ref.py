@@ -1,6 +1,6 @@
 """Shared by test_fa_dkv_cpu.py and test_fa_dkv_gpu.py: inputs, the fp64
 reference of the flash-attention dK/dV backward, its bound, and a torch
-emulation of the kernel's design (csrc/kernels/flash_attn.hip,
+emulation of the kernel's design (csrc/kernels/fa_bwd.hip,
 fa_bwd_dkv_kernel).  Everything here runs on the CPU.
 
 Reference, from the bf16 inputs (upcast, so exactly what the kernel reads):

@@ -34,7 +34,7 @@ def test_extension_loaded():
 
 def test_mfma_fragment_layout_probe():
     """Asymmetric-input MFMA probe (guide G9): validates the A/B/C lane
-    mappings used by flash_attn.hip."""
+    mappings used by fa_bwd.hip."""
     C = _ext.get_ext()
     torch.manual_seed(0)
     a = torch.randn(16, 32, device=DEV)
