@@ -856,11 +856,14 @@ void kv_quant_append(const Tensor& k, const Tensor& v, const Tensor& kcache,
 // workspaces.  Every check precedes any launch.  `dense` is null for the
 // paged layout [nblocks, bs, HKV, D]; else {blk, pos, head, bs}: the caller's
 // element strides and block size over bf16 caches [nblocks, HKV, ., D].
+// `batch` is null where q is [B, H, D]; paged_prefill_attention passes its B
+// for q [T, H, D].
 static pa::DecodeAttnArgs check_paged_decode(
     const char* op, const Tensor& q, const Tensor& kcache,
     const Tensor& vcache, const Tensor& block_table, const Tensor& seq_lens,
     const c10::optional<Tensor>& k_scale, const c10::optional<Tensor>& v_scale,
-    int64_t nsplit, const int64_t* dense = nullptr) {
+    int64_t nsplit, const int64_t* dense = nullptr,
+    const int64_t* batch = nullptr) {
   TORCH_CHECK(q.is_cuda(), op, ": q must be a GPU tensor");
   TORCH_CHECK(k_scale.has_value() == v_scale.has_value(), op,
               ": give both k_scale and v_scale or neither");
@@ -891,7 +894,8 @@ static pa::DecodeAttnArgs check_paged_decode(
               q.is_contiguous(), op, ": q must be contiguous bfloat16 [B, H, D]");
   TORCH_CHECK(reinterpret_cast<uintptr_t>(q.const_data_ptr()) % 16 == 0, op,
               ": q must start 16-byte aligned");
-  const int64_t b = q.size(0), h = q.size(1), d = q.size(2);
+  // prefill: q is [T, H, D] and the batch is the table's
+  const int64_t b = batch ? *batch : q.size(0), h = q.size(1), d = q.size(2);
   const int64_t nblocks = kcache.size(0);
   const int64_t bs = dense ? dense[3] : kcache.size(1);
   const int64_t hkv = kcache.size(dense ? 1 : 2);
@@ -1009,6 +1013,51 @@ Tensor decode_attention_split(const Tensor& q, const Tensor& kcache,
   return launch_paged_decode(
       check_paged_decode(op, q, kcache, vcache, block_table, seq_lens, k_scale,
                          v_scale, num_splits), q, scale);
+}
+
+// ---- paged prefill attention -------------------------------------------------
+// docs/KERNELS.md "paged prefill attention".  Caches, scales and table by
+// check_paged_decode; every check precedes any launch or allocation.
+Tensor paged_prefill_attention(const Tensor& q, const Tensor& kcache,
+                               const Tensor& vcache, const Tensor& block_table,
+                               const Tensor& seq_lens, const Tensor& cu_q,
+                               int64_t max_q, double scale,
+                               const c10::optional<Tensor>& k_scale,
+                               const c10::optional<Tensor>& v_scale) {
+  const char* op = "paged_prefill_attention";
+  TORCH_CHECK(block_table.dim() == 2, op,
+              ": block_table must be contiguous int32 [B, max_blocks]");
+  const int64_t b = block_table.size(0);
+  const pa::DecodeAttnArgs d =
+      check_paged_decode(op, q, kcache, vcache, block_table, seq_lens, k_scale,
+                         v_scale, 0, nullptr, &b);
+  const int64_t t = q.size(0), lim = 1LL << 31;
+  TORCH_CHECK(cu_q.is_cuda() && cu_q.device() == q.device() &&
+              cu_q.scalar_type() == torch::kInt && cu_q.dim() == 1 &&
+              cu_q.size(0) == b + 1 && cu_q.is_contiguous(), op,
+              ": cu_q must be contiguous int32 [B + 1]");
+  TORCH_CHECK(max_q >= 1 && max_q < lim && max_q * (d.h / d.hkv) < lim, op,
+              ": need 1 <= max_q and max_q * H / HKV < 2^31, got ", max_q);
+  TORCH_CHECK(t * d.h < lim, op, ": T * H must be below 2^31");
+  TORCH_CHECK(b <= 65535 && d.hkv <= 65535, op,
+              ": B and HKV must be at most 65535 (grid dimensions)");
+  TORCH_CHECK(b >= 1 || t == 0, op, ": tokens without a sequence");
+  if (t == 0) return torch::empty_like(q);
+  auto o = torch::empty_like(q);
+  pa::PrefillAttnArgs a{};
+  a.q = d.q; a.kcache = d.kcache; a.vcache = d.vcache;
+  a.kscale = d.kscale; a.vscale = d.vscale;
+  a.block_table = d.block_table; a.seq_lens = d.seq_lens;
+  a.cu_q = cu_q.const_data_ptr<int>();
+  a.o = o.mutable_data_ptr();
+  a.b = d.b; a.h = d.h; a.hkv = d.hkv; a.bs = d.bs;
+  a.max_blocks = d.max_blocks; a.nblocks = d.nblocks; a.dh = d.dh;
+  a.t = (int)t; a.max_q = (int)max_q;
+  a.scale = (float)scale;
+  a.cs_blk = d.cs_blk; a.cs_pos = d.cs_pos; a.cs_head = d.cs_head;
+  a.ss_blk = d.ss_blk; a.ss_pos = d.ss_pos; a.ss_head = d.ss_head;
+  pa::paged_prefill_attention(a, cur_stream());
+  return o;
 }
 
 // ---- hand-written GEMM ----------------------------------------------------
@@ -1478,6 +1527,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("kcache"), py::arg("vcache"), py::arg("block_table"),
         py::arg("seq_lens"), py::arg("scale"), py::arg("num_splits"),
         py::arg("k_scale") = c10::nullopt, py::arg("v_scale") = c10::nullopt);
+  m.def("paged_prefill_attention", &paged_prefill_attention, py::arg("q"),
+        py::arg("kcache"), py::arg("vcache"), py::arg("block_table"),
+        py::arg("seq_lens"), py::arg("cu_q"), py::arg("max_q"),
+        py::arg("scale"), py::arg("k_scale") = c10::nullopt,
+        py::arg("v_scale") = c10::nullopt);
   m.def("decode_attn_split_grid", &decode_attn_split_grid, py::arg("b"),
         py::arg("h"), py::arg("hkv"), py::arg("num_splits"), py::arg("int8"));
   m.def("mfma_probe", &mfma_probe);

@@ -220,6 +220,28 @@ struct DecodeAttnArgs {
 };
 void decode_attention(const DecodeAttnArgs& a, hipStream_t s);
 
+// ---- paged prefill attention (prefill_attn.hip) ----------------------------
+// q_len_b = cu_q[b+1] - cu_q[b] >= 1 new tokens per sequence attend to the
+// paged cache.  q, o bf16 [t, h, dh] packed over sequences; cu_q int32
+// [b + 1]; caches, scales, table and their cs_* / ss_* strides as in
+// DecodeAttnArgs (paged layout only).  seq_lens[b] counts the new tokens;
+// S_b = max(0, min(seq_lens[b], max_blocks * bs)); token i of sequence b
+// sits at position S_b - q_len_b + i and sees positions 0 .. that one.
+// Grid (ceil(max_q * h / hkv / 64), hkv, b): rows of a sequence with
+// q_len_b > max_q past the grid are not computed.  No workspace, no atomics,
+// no host read.
+struct PrefillAttnArgs {
+  const void *q, *kcache, *vcache;
+  const float *kscale, *vscale;
+  const int *block_table, *seq_lens, *cu_q;
+  void* o;
+  int b, h, hkv, bs, max_blocks, nblocks, dh, t, max_q;
+  float scale;
+  long long cs_blk, cs_pos, cs_head;
+  long long ss_blk, ss_pos, ss_head;
+};
+void paged_prefill_attention(const PrefillAttnArgs& a, hipStream_t s);
+
 // ---- hand-written bf16 MFMA GEMM (C[m][n] = op(A) x op(B)) ----------------
 // b_is_nt: B passed as Bt[n][k] row-major (fast path); else B[k][n].
 void gemm_bf16_8p(const void* a, const void* b, void* c, int64_t m, int64_t n,

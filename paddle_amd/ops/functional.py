@@ -1249,6 +1249,24 @@ def _decode_attn_split_plan(B, H, HKV, D, capacity, int8):
     return max(int(n), 1)
 
 
+def _paged_caches_ok(k_cache, v_cache, k_scale, v_scale):
+    """The paged pools of the attention bindings: int8 pools per
+    _kv_int8_pools_ok with scales, bf16 contiguous [nblocks, bs, HKV, D]
+    caches of equal shape without; 16-byte aligned."""
+    if (k_scale is None) != (v_scale is None):
+        return False
+    if k_scale is not None:
+        if not (_kv_int8_pools_ok(k_cache, v_cache, k_scale, v_scale)):
+            return False
+    elif not (k_cache.dtype == torch.bfloat16
+              and v_cache.dtype == torch.bfloat16 and k_cache.dim() == 4
+              and k_cache.shape == v_cache.shape and k_cache.is_contiguous()
+              and v_cache.is_contiguous() and k_cache.numel() > 0):
+        return False
+    return not any((t.storage_offset() * t.element_size()) % 16
+                   for t in (k_cache, v_cache))
+
+
 def _paged_decode_native_ok(q, k_cache, v_cache, block_table, seq_lens,
                             k_scale=None, v_scale=None):
     """Contract of decode_attention / decode_attention_int8 /
@@ -1267,16 +1285,7 @@ def _paged_decode_native_ok(q, k_cache, v_cache, block_table, seq_lens,
         return False
     if any(t.device != q.device for t in ts):
         return False
-    if k_scale is not None:
-        if not (_kv_int8_pools_ok(k_cache, v_cache, k_scale, v_scale)):
-            return False
-    elif not (k_cache.dtype == torch.bfloat16
-              and v_cache.dtype == torch.bfloat16 and k_cache.dim() == 4
-              and k_cache.shape == v_cache.shape and k_cache.is_contiguous()
-              and v_cache.is_contiguous() and k_cache.numel() > 0):
-        return False
-    if any((t.storage_offset() * t.element_size()) % 16
-           for t in (k_cache, v_cache)):
+    if not _paged_caches_ok(k_cache, v_cache, k_scale, v_scale):
         return False
     if not (q.dtype == torch.bfloat16 and q.dim() == 3):
         return False
@@ -1372,6 +1381,126 @@ def paged_decode_attention(q, k_cache, v_cache, block_table, seq_lens, scale=Non
         s = torch.einsum("hd,shd->hs", q[b].float(), kf) * scale
         p = torch.softmax(s, dim=-1)
         out[b] = torch.einsum("hs,shd->hd", p, vf).to(q.dtype)
+    return out
+
+
+# Paged prefill attention (docs/KERNELS.md "paged prefill attention").
+def _paged_prefill_native_ok(q, k_cache, v_cache, block_table, seq_lens, cu_q,
+                             max_q, k_scale=None, v_scale=None):
+    """Contract of the paged_prefill_attention binding (pure: dtypes, shapes,
+    strides, devices; mirrors paged_prefill_attention in csrc/bindings.cpp).
+    Caches, scales and their alignment as in _paged_decode_native_ok; q bf16
+    [T, H, D] (the dispatch site passes it contiguous) 16-byte aligned, D in
+    {64, 128} equal to the cache's, H % HKV == 0; block_table
+    [B, max_blocks], seq_lens [B] and cu_q [B + 1] integer tensors (the site
+    casts them to int32) on q's device; max_q an integer with 1 <= max_q and
+    max_q * H / HKV < 2^31; T * H < 2^31, max_blocks * bs < 2^31; B and HKV
+    at most 65535 (grid dimensions); B >= 1 unless T == 0."""
+    ts = (q, k_cache, v_cache, block_table, seq_lens, cu_q)
+    if not all(isinstance(t, torch.Tensor) for t in ts):
+        return False
+    if block_table.dim() != 2 or q.dim() != 3:
+        return False
+    B = block_table.shape[0]
+    if any(t.device != q.device for t in ts):
+        return False
+    if not _paged_caches_ok(k_cache, v_cache, k_scale, v_scale):
+        return False
+    if q.dtype != torch.bfloat16:
+        return False
+    d = q.shape[2]
+    if d not in (64, 128) or d != k_cache.shape[3] or q.shape[1] == 0 \
+            or q.shape[1] % k_cache.shape[2]:
+        return False
+    if q.is_contiguous() and (q.storage_offset() * 2) % 16:
+        return False
+    ints = (torch.int32, torch.int64)
+    if not (block_table.dtype in ints and seq_lens.dim() == 1
+            and seq_lens.shape[0] == B and seq_lens.dtype in ints
+            and cu_q.dim() == 1 and cu_q.shape[0] == B + 1
+            and cu_q.dtype in ints):
+        return False
+    if isinstance(max_q, bool) or not isinstance(max_q, int) or max_q < 1:
+        return False
+    T, H = q.shape[0], q.shape[1]
+    bs, HKV = k_cache.shape[1], k_cache.shape[2]
+    lim = 1 << 31
+    return (max_q * (H // HKV) < lim and T * H < lim
+            and block_table.shape[1] * bs < lim and k_cache.shape[0] < lim
+            and B <= 65535 and HKV <= 65535 and (B >= 1 or T == 0))
+
+
+def paged_prefill_attention(q, k_cache, v_cache, block_table, seq_lens, cu_q,
+                            max_q, scale=None, k_scale=None, v_scale=None):
+    """Attention of q_len_b >= 1 new tokens per sequence over the paged cache.
+    q: [T, H, D] packed over sequences; cu_q: int [B + 1] prefix sums,
+    q_len_b = cu_q[b+1] - cu_q[b]; k/v_cache, block_table [B, max_blocks],
+    k_scale/v_scale: the pools of paged_decode_attention.  seq_lens[b] is the
+    cached length INCLUDING the new tokens (append them first);
+    S_b = clamp(seq_lens[b], 0, max_blocks * bs).  Token i of sequence b sits
+    at position S_b - q_len_b + i and sees positions 0 .. that one
+    (bottom-right causal); a row that sees nothing is zero.  A table entry
+    outside [0, nblocks) contributes nothing.
+    max_q: host integer >= max_b q_len_b; it sizes the kernel's grid so that
+    nothing is read on the host.  Rows of a sequence with q_len_b > max_q are
+    outside the contract: the kernel leaves the surplus rows (unspecified
+    values, nothing out of bounds); so are tokens that no sequence covers.
+    Outside _paged_prefill_native_ok, on CPU or with native kernels off, the
+    torch path below answers (it reads seq_lens and cu_q on the host)."""
+    if scale is None:
+        scale = 1.0 / math.sqrt(q.shape[-1])
+    int8 = k_scale is not None or v_scale is not None
+    if int8:
+        if k_scale is None or v_scale is None:
+            raise ValueError("paged_prefill_attention: give both k_scale and "
+                             "v_scale or neither")
+        if not _kv_int8_pools_ok(k_cache, v_cache, k_scale, v_scale):
+            raise ValueError(
+                "paged_prefill_attention: k_scale/v_scale need int8 contiguous "
+                "[nblocks, bs, HKV, D] caches of equal shape and fp32 "
+                "contiguous scales [nblocks, bs, HKV] or [HKV]")
+    if _ext.use_native(q) and _paged_prefill_native_ok(
+            q, k_cache, v_cache, block_table, seq_lens, cu_q, max_q, k_scale,
+            v_scale):
+        return _ext.get_ext().paged_prefill_attention(
+            q.contiguous(), k_cache, v_cache, block_table.int().contiguous(),
+            seq_lens.int().contiguous(), cu_q.int().contiguous(), int(max_q),
+            scale, k_scale, v_scale)
+    # reference: gather each sequence's KV, masked softmax in fp32
+    T, H, D = q.shape
+    nblocks, bs, HKV = k_cache.shape[0], k_cache.shape[1], k_cache.shape[2]
+    rep = H // HKV
+    out = torch.zeros_like(q)
+    cu = [int(x) for x in cu_q.tolist()]
+    lens = [int(x) for x in seq_lens.tolist()]
+    for b in range(block_table.shape[0]):
+        lo, hi = max(cu[b], 0), min(cu[b + 1], T)
+        q_len = cu[b + 1] - cu[b]
+        if q_len <= 0 or lo >= hi:
+            continue
+        S = max(0, min(lens[b], block_table.shape[1] * bs))
+        if S == 0:
+            continue
+        blocks = block_table[b, :(S + bs - 1) // bs].long()
+        inside = (blocks >= 0) & (blocks < nblocks)
+        blocks = blocks.clamp(0, nblocks - 1)
+        if int8:
+            k = _kv_int8_dequant_rows(k_cache, k_scale, blocks, S)
+            v = _kv_int8_dequant_rows(v_cache, v_scale, blocks, S)
+        else:
+            k = k_cache[blocks].reshape(-1, HKV, D)[:S]
+            v = v_cache[blocks].reshape(-1, HKV, D)[:S]
+        kf = k.float().repeat_interleave(rep, dim=1)   # [S, H, D]
+        vf = v.float().repeat_interleave(rep, dim=1)
+        i = torch.arange(lo - cu[b], hi - cu[b], device=q.device)
+        pos = torch.arange(S, device=q.device)
+        seen = (pos[None, :] <= (S - q_len + i)[:, None]) \
+            & inside.repeat_interleave(bs)[:S][None, :]       # [q, S]
+        s = torch.einsum("qhd,shd->qhs", q[lo:hi].float(), kf) * scale
+        s = s.masked_fill(~seen[:, None, :], float("-inf"))
+        p = torch.softmax(s, dim=-1).masked_fill(~seen[:, None, :], 0.0)
+        p = torch.nan_to_num(p, nan=0.0)               # a row that sees nothing
+        out[lo:hi] = torch.einsum("qhs,shd->qhd", p, vf).to(q.dtype)
     return out
 
 

@@ -232,17 +232,32 @@ class GenerationServer:
 class GPTModelRunner:
     """Engine step_fn for GPTForPretraining: per-request block tables from
     the engine's allocator, one batched paged-decode step per call.
-    Admission prefills the new request through the flash-attention path;
-    decode runs every active request through `paged_decode_attention`."""
+    Admission prefills the new request through the flash-attention path, or
+    with prefill_chunk=N at most N prompt tokens per call through
+    `paged_prefill_attention` over the cache; decode runs every active
+    request through `paged_decode_attention`."""
 
     def __init__(self, model, num_blocks=1024, block_size=16,
                  device=None, dtype=None, max_seq=2048, use_graphs=True,
                  weight_only=False, weight_only_group_size=-1,
-                 kv_cache="bf16", decode_splits=None):
+                 kv_cache="bf16", decode_splits=None, prefill_chunk=None):
         import math
         from .ops import functional as hot
         self.hot = hot
         self.model = model.eval()
+        # prefill_chunk=None: a prompt is prefilled whole, in one
+        # flash-attention pass, when its request is admitted.  N >= 1:
+        # chunked prefill -- each call gives the prefilling requests, in
+        # admission order, at most N prompt tokens in all and runs them as one
+        # packed pass through paged_prefill_attention over the cache
+        # (docs/SERVING.md "chunked prefill")
+        if prefill_chunk is not None and (
+                isinstance(prefill_chunk, bool)
+                or not isinstance(prefill_chunk, int) or prefill_chunk < 1):
+            raise ValueError("prefill_chunk must be None or an integer >= 1, "
+                             f"got {prefill_chunk!r}")
+        self.prefill_chunk = prefill_chunk
+        self._prefilled = {}         # rid -> prompt tokens cached so far
         # decode_splits -> paged_decode_attention(num_splits=): None lets the
         # shape heuristic choose (bucket B and max_seq only, so each bucket's
         # graph is fixed), 0 pins the one-block-per-q-head kernels, n >= 1
@@ -351,11 +366,84 @@ class GPTModelRunner:
                                                   r.top_p)
 
     @torch.no_grad()
+    def _prefill_chunked(self, reqs, blocks):
+        """One chunked-prefill pass: the prefilling requests `reqs`, in
+        admission order, take prompt tokens until prefill_chunk tokens are
+        used up; those T <= prefill_chunk tokens run as one packed pass.
+        Returns {rid: first generated token} of the requests whose prompt
+        completed; the others stay prefilling."""
+        N = self.prefill_chunk
+        budget, take = N, []
+        for r in reqs:
+            if budget == 0:
+                break
+            done = self._prefilled.get(r.rid, 0)
+            n = min(budget, len(r.prompt_ids) - done)
+            take.append((r, done, n))
+            budget -= n
+        ids, pos, blk, off, rows, lens, cu, last, fin = [], [], [], [], [], [], [0], [], []
+        for r, done, n in take:
+            bl = blocks[r.rid]
+            ids += r.prompt_ids[done:done + n]
+            pos += range(done, done + n)
+            blk += [bl[p // self.bs] for p in range(done, done + n)]
+            off += [p % self.bs for p in range(done, done + n)]
+            rows.append(bl + [0] * (self.max_blk - len(bl)))
+            lens.append(done + n)            # cached so far + this chunk
+            cu.append(cu[-1] + n)
+            if done + n == len(r.prompt_ids):
+                last.append(cu[-1] - 1)
+                fin.append(r)
+
+        def dev(x, dt):
+            return torch.tensor(x, dtype=dt).to(self.dev, non_blocking=True)
+        x = self._chunk_forward(dev(ids, torch.long), dev(pos, torch.long),
+                                dev(blk, torch.long), dev(off, torch.long),
+                                dev(rows, torch.int32), dev(lens, torch.int32),
+                                dev(cu, torch.int32))
+        for r, done, n in take:
+            self._prefilled[r.rid] = done + n
+        out = {}
+        if fin:
+            logits = self._chunk_logits(x[dev(last, torch.long)])
+            for i, r in enumerate(fin):
+                del self._prefilled[r.rid]
+                self.seq_len[r.rid] = len(r.prompt_ids)
+                self.last_token[r.rid] = sample_token(logits[i], r.temperature,
+                                                      r.top_p)
+                out[r.rid] = self.last_token[r.rid]
+        return out
+
+    def _chunk_forward(self, ids, pos, blk, off, table, lens, cu_q):
+        """Hidden states [T, hidden] of T packed prompt tokens at their own
+        positions `pos`; their K/V go to (blk, off) of every layer before the
+        layer's attention reads the cache."""
+        m = self.model
+        T = ids.shape[0]
+        x = m.gpt.embeddings(ids[None], pos[None])
+        for li, layer in enumerate(m.gpt.layers):
+            h = layer.ln1(x)
+            q, k, v = self._qkv(layer, h)
+            self._kv_write(li, blk, off, k[0], v[0])
+            att = self.hot.paged_prefill_attention(
+                q[0], self.k[li], self.v[li], table, lens, cu_q,
+                self.prefill_chunk, self.scale,
+                k_scale=self.k_scale[li], v_scale=self.v_scale[li])
+            x = x + layer.attn.out_proj(att.reshape(1, T, -1))
+            x = x + layer.mlp(layer.ln2(x))
+        return x[0]
+
+    def _chunk_logits(self, x):
+        return self.model.lm_head(self.model.gpt.final_norm(x))
+
+    @torch.no_grad()
     def __call__(self, active, blocks):
         m = self.model
         out = {}
         new = [r for r in active if r.rid not in self.seq_len]
-        if new:
+        if new and self.prefill_chunk is not None:
+            out.update(self._prefill_chunked(new, blocks))
+        elif new:
             by_len = {}
             for r in new:
                 by_len.setdefault(len(r.prompt_ids), []).append(r)
@@ -599,6 +687,29 @@ class LlamaModelRunner(GPTModelRunner):
             self.seq_len[r.rid] = S0
             self.last_token[r.rid] = sample_token(logits[i], r.temperature,
                                                   r.top_p)
+
+    def _chunk_forward(self, ids, pos, blk, off, table, lens, cu_q):
+        m = self.model
+        T = ids.shape[0]
+        x = m.llama.embed_tokens(ids[None])
+        for li, layer in enumerate(m.llama.layers):
+            h = layer.input_layernorm(x).reshape(T, -1)
+            a = layer.self_attn
+            # rope at each token's own position (the decode path's gather)
+            q = self._rope_rows(a.q_proj(h).reshape(T, 1, self.H, self.D), pos)
+            k = self._rope_rows(a.k_proj(h).reshape(T, 1, self.HKV, self.D), pos)
+            v = a.v_proj(h).reshape(T, self.HKV, self.D)
+            self._kv_write(li, blk, off, k[:, 0], v)
+            att = self.hot.paged_prefill_attention(
+                q[:, 0], self.k[li], self.v[li], table, lens, cu_q,
+                self.prefill_chunk, self.scale,
+                k_scale=self.k_scale[li], v_scale=self.v_scale[li])
+            x = x + a.o_proj(att.reshape(1, T, -1))
+            x = x + layer.mlp(layer.post_attention_layernorm(x))
+        return x[0]
+
+    def _chunk_logits(self, x):
+        return self.model.lm_head(self.model.llama.norm(x))
 
     def _decode_forward(self, B, toks, pos_ids, table, lens, write_blk,
                         write_off):

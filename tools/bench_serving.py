@@ -19,7 +19,8 @@ from paddle_amd.serving import Engine, GPTModelRunner, Request  # noqa: E402
 
 def run_one(tag, model, n_req=64, prompt_len=128, gen_len=128, max_batch=32,
             num_blocks=4096, weight_only=False, runner_cls="gpt",
-            group_size=-1, kv_cache="bf16", decode_splits=None):
+            group_size=-1, kv_cache="bf16", decode_splits=None,
+            prefill_chunk=None):
     cls = GPTModelRunner
     if runner_cls == "llama":
         from paddle_amd.serving import LlamaModelRunner
@@ -27,7 +28,8 @@ def run_one(tag, model, n_req=64, prompt_len=128, gen_len=128, max_batch=32,
     runner = cls(model, num_blocks=num_blocks, block_size=16,
                  max_seq=max(2048, prompt_len + gen_len),
                  weight_only=weight_only, weight_only_group_size=group_size,
-                 kv_cache=kv_cache, decode_splits=decode_splits)
+                 kv_cache=kv_cache, decode_splits=decode_splits,
+                 prefill_chunk=prefill_chunk)
     pools = runner.k + runner.v + [s for s in runner.k_scale + runner.v_scale
                                    if s is not None]
     pool_gb = sum(t.numel() * t.element_size() for t in pools) / 2**30
@@ -42,7 +44,9 @@ def run_one(tag, model, n_req=64, prompt_len=128, gen_len=128, max_batch=32,
             prompt_ids=[random.randrange(V) for _ in range(prompt_len)],
             max_new_tokens=gen_len))
     t0 = time.perf_counter()
-    eng.step()                      # prefill wave (all same-length prompts)
+    # prefill wave (all same-length prompts); with --prefill-chunk only the
+    # first chunk, and the steps counted below interleave prefill and decode
+    eng.step()
     torch.cuda.synchronize()
     t1 = time.perf_counter()
     tok0 = sum(len(r.out_ids) for r in (eng.active + eng.completed + eng.waiting))
@@ -88,6 +92,9 @@ def main():
     ap.add_argument("--decode-splits", type=int, default=None,
                     help="runner decode_splits: unset = heuristic, 0 = "
                          "one-block-per-q-head kernels, n = split-KV kernels")
+    ap.add_argument("--prefill-chunk", type=int, default=None,
+                    help="runner prefill_chunk: unset = whole-prompt prefill, "
+                         "n = at most n prompt tokens per engine step")
     args = ap.parse_args()
     paddle.seed(0)
     wo = args.weight_only_dtype or ("int8" if args.weight_only else False)
@@ -98,12 +105,15 @@ def main():
         tag_sfx += f" {args.kv_cache}-kv"
     if args.decode_splits is not None:
         tag_sfx += f" splits={args.decode_splits}"
+    if args.prefill_chunk is not None:
+        tag_sfx += f" chunk={args.prefill_chunk}"
     if args.max_batch != 32:
         tag_sfx += f" b{args.max_batch}"
     kw = dict(weight_only=wo, group_size=args.group_size,
               kv_cache=args.kv_cache, prompt_len=args.prompt_len,
               gen_len=args.gen_len, n_req=args.n_req,
-              max_batch=args.max_batch, decode_splits=args.decode_splits)
+              max_batch=args.max_batch, decode_splits=args.decode_splits,
+              prefill_chunk=args.prefill_chunk)
     seq = max(2048, args.prompt_len + args.gen_len)
     # blocks for max_batch sequences of prompt+gen tokens, with headroom
     nblk = max(8192, 2 * 32 * (-(-seq // 16)))
