@@ -12,7 +12,8 @@
 //   * fa_bwd_dkv32_kernel: dK or dV (one launch each) for mask, dropout and
 //     varlen.  MFMA 32x32x16, 4 waves.
 //   * fa_bwd_dq32_kernel: dQ for every path.  MFMA 32x32x16, 4 waves, the
-//     forward's swapped layout.
+//     forward's swapped layout and its double-buffered K / V image, K read
+//     by rows and by columns.
 #include "fa_common.h"
 
 namespace pa {
@@ -457,8 +458,16 @@ __global__ void fa_bwd_dkv_kernel(const short* __restrict__ dog, const short* __
 // dP^T put the q-COLUMN in each lane (per-lane lse/delta, no broadcasts),
 // and the dS A-fragments for dQ += dS.K are assembled with the identical
 // static-pack + permlane32_swap exchange (no LDS round trip).
-// K/V staged natural via async DMA; K^T staged with rotated writes for the
-// dQ B-fragments.
+// K and V land once per tile, by DMA, in the natural [64 kv][D] image of the
+// forward (fa_common.h, fa_kv_off).  The K image feeds S^T by ds_read_b128
+// rows and dQ += dS K by ds_read_b64_tr_b16, so K is read once from global
+// and no transposed copy is built; V takes row reads only.  Two {K, V}
+// buffers, tile t+1 in flight under tile t's math, one barrier per tile.
+// Every MFMA gets the operands, in the k order, of the kernel this replaces
+// (K^T by scalar writes, one buffer), so dQ is bit-identical to it.
+// Measured, B12 H32 S2048 D128 causal: 1369 -> 877 us per call in the
+// flagship trace, SQ_LDS_BANK_CONFLICT 1.4e8 -> 0, 256 VGPR + 12 B scratch ->
+// 248 VGPR and none (docs/KERNELS.md, "forward and dQ").
 // ---------------------------------------------------------------------------
 template <int D, bool CAUSAL, bool MASKED, bool DROPOUT, bool VARLEN>
 __launch_bounds__(256, 2)
@@ -484,11 +493,9 @@ __global__ void fa_bwd_dq32_kernel(const short* __restrict__ dog, const short* _
   constexpr int KB = 64;
   constexpr int NKS = D / 16;
   constexpr int NDT = D / 32;
-  constexpr unsigned NAT_RS = D * 2;
-  constexpr unsigned KT_RS = KB * 2;
-  __shared__ char k_lds[KB * D * 2];
-  __shared__ char v_lds[KB * D * 2];
-  __shared__ char kt_lds[D * KB * 2];
+  constexpr int TILE = KB * D * 2;  // bytes of one [64][D] tile
+  // one array: two {K, V} buffers (fa_common.h, fa_stage_kv)
+  __shared__ __attribute__((aligned(16))) char lds[4 * TILE];
 
   const int qblk = blockIdx.y;      // slow dim: global longest-first causal order
   const int bh = blockIdx.x;
@@ -554,65 +561,31 @@ __global__ void fa_bwd_dq32_kernel(const short* __restrict__ dog, const short* _
 #pragma unroll
     for (int r = 0; r < 16; ++r) dq_acc[dt][r] = 0.f;
 
-  // DMA staging maps
-  constexpr unsigned KSWZ = (D >= 128) ? 15u : 7u;
-  int n_row[KB * D / (NT * 8)], n_colp[KB * D / (NT * 8)];
+  // LDS addresses of the lane's rows for the transposed reads of K
+  const unsigned lds_a = (unsigned)(size_t)(__attribute__((address_space(3))) char*)lds;
+  unsigned tr_a[2][NDT];   // even, odd k-steps
 #pragma unroll
-  for (int it = 0; it < KB * D / (NT * 8); ++it) {
-    int flat = it * NT * 8 + tid * 8;
-    int row = flat / D, col = flat % D;
-    n_row[it] = row;
-    n_colp[it] = col ^ ((row & (int)KSWZ) << 3);
+  for (int dt = 0; dt < NDT; ++dt) {
+    tr_a[0][dt] = fa_tr_addr<D>(lds_a, lane, dt, 0);
+    tr_a[1][dt] = fa_tr_addr<D>(lds_a, lane, dt, 16);
   }
 
   const int kv_end = CAUSAL ? min(Skv_e, q0 + QB + cdelta) : Skv_e;
+  if (kv_end > 0) fa_stage_kv<D, NT>(lds, kg, vg, kvbase, k_ss, 0, Skv_e, tid);
+  int cur = 0;
   for (int kv0 = 0; kv0 < kv_end; kv0 += KB) {
-    if (kv0 + KB <= Skv_e) {
-#pragma unroll
-      for (int it = 0; it < KB * D / (NT * 8); ++it) {
-        const short* ksrc = kg + kvbase + (long long)(kv0 + n_row[it]) * k_ss + n_colp[it];
-        const short* vsrc = vg + kvbase + (long long)(kv0 + n_row[it]) * k_ss + n_colp[it];
-        __builtin_amdgcn_global_load_lds(
-            (const __attribute__((address_space(1))) unsigned int*)ksrc,
-            (__attribute__((address_space(3))) unsigned int*)(k_lds + it * NT * 16 + (tid >> 6) * 64 * 16),
-            16, 0, 0);
-        __builtin_amdgcn_global_load_lds(
-            (const __attribute__((address_space(1))) unsigned int*)vsrc,
-            (__attribute__((address_space(3))) unsigned int*)(v_lds + it * NT * 16 + (tid >> 6) * 64 * 16),
-            16, 0, 0);
-      }
-      const int rot = tid & 7;
-      for (int flat = tid * 8; flat < KB * D; flat += NT * 8) {
-        int row = flat / D, col = flat % D;
-        shortx8 kv_ = *reinterpret_cast<const shortx8*>(
-            kg + kvbase + (long long)(kv0 + row) * k_ss + col);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          int i = (j + rot) & 7;
-          *reinterpret_cast<short*>(kt_lds + lds_off32(col + i, row * 2, KT_RS)) = kv_[i];
-        }
-      }
-    } else {
-      for (int flat = tid * 8; flat < KB * D; flat += NT * 8) {
-        int row = flat / D, col = flat % D;
-        shortx8 kv_, vv;
-        if (kv0 + row < Skv_e) {
-          kv_ = *reinterpret_cast<const shortx8*>(kg + kvbase + (long long)(kv0 + row) * k_ss + col);
-          vv = *reinterpret_cast<const shortx8*>(vg + kvbase + (long long)(kv0 + row) * k_ss + col);
-        } else {
-          for (int i = 0; i < 8; ++i) { kv_[i] = 0; vv[i] = 0; }
-        }
-        *reinterpret_cast<shortx8*>(k_lds + lds_off32w(row, col * 2, NAT_RS, KSWZ)) = kv_;
-        *reinterpret_cast<shortx8*>(v_lds + lds_off32w(row, col * 2, NAT_RS, KSWZ)) = vv;
-        const int rot = tid & 7;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          int i = (j + rot) & 7;
-          *reinterpret_cast<short*>(kt_lds + lds_off32(col + i, row * 2, KT_RS)) = kv_[i];
-        }
-      }
-    }
+    // Tile kv0 was issued one tile ago (or in the prologue) and nothing newer
+    // is in flight, so the counted wait is vmcnt(0).  The one barrier per
+    // tile says both "tile kv0 has landed for every wave" and "every wave is
+    // done reading tile kv0-KB", which frees the other buffer.
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
+    const unsigned boff = cur * (2 * TILE);
+    const char* k_t = lds + boff;
+    const char* v_t = k_t + TILE;
+    if (kv0 + KB < kv_end)
+      fa_stage_kv<D, NT>(lds + (cur ^ 1) * (2 * TILE), kg, vg, kvbase, k_ss, kv0 + KB, Skv_e, tid);
+    cur ^= 1;
 
     // ---- S^T = K Q^T and dP^T = V dO^T ------------------------------------
     floatx16 st[2], dp[2];
@@ -623,10 +596,10 @@ __global__ void fa_bwd_dq32_kernel(const short* __restrict__ dog, const short* _
 #pragma unroll
       for (int ks = 0; ks < NKS; ++ks) {
         shortx8 kf = *reinterpret_cast<const shortx8*>(
-            k_lds + lds_off32w(t * 32 + l32, (ks * 16 + hi * 8) * 2, NAT_RS, KSWZ));
+            k_t + fa_kv_off<D>(t * 32 + l32, ks * 2 + hi));
         st[t] = mfma32_bf16(kf, qf[ks], st[t]);
         shortx8 vf = *reinterpret_cast<const shortx8*>(
-            v_lds + lds_off32w(t * 32 + l32, (ks * 16 + hi * 8) * 2, NAT_RS, KSWZ));
+            v_t + fa_kv_off<D>(t * 32 + l32, ks * 2 + hi));
         dp[t] = mfma32_bf16(vf, dof[ks], dp[t]);
       }
     }
@@ -681,11 +654,13 @@ __global__ void fa_bwd_dq32_kernel(const short* __restrict__ dog, const short* _
     }
 
     // ---- dQ += dS K (A-frags via static packs + permlane exchange) --------
-#pragma unroll
-    for (int ks = 0; ks < KB / 16; ++ks) {
-      const int t = ks >> 1;
-      const int kp = ks & 1;
-      const int b0 = 8 * kp;
+    // one k-step of 16 kv rows; KS is a type so the offsets of the
+    // transposed reads are immediates
+    auto dq_step = [&](auto KS) {
+      constexpr int ks = decltype(KS)::value;
+      constexpr int t = ks >> 1;
+      constexpr int kp = ks & 1;
+      constexpr int b0 = 8 * kp;
       int P0 = pack_bf2(st[t][b0 + 0], st[t][b0 + 1]);
       int P1 = pack_bf2(st[t][b0 + 2], st[t][b0 + 3]);
       int P2 = pack_bf2(st[t][b0 + 4], st[t][b0 + 5]);
@@ -704,14 +679,20 @@ __global__ void fa_bwd_dq32_kernel(const short* __restrict__ dog, const short* _
       paw[2] = hi ? O1 : X1;
       paw[3] = hi ? O2 : X2;
       shortx8 pa = *reinterpret_cast<shortx8*>(&paw);
+      // B[k = 16*ks + 8*hi + 0..7][n = 32*dt + l32] of K, by transposed reads
+      // of the image that fed S^T by rows
+      shortx8 bf[NDT];
+      unsigned ka[NDT];
 #pragma unroll
-      for (int dt = 0; dt < NDT; ++dt) {
-        shortx8 bf = *reinterpret_cast<const shortx8*>(
-            kt_lds + lds_off32(dt * 32 + l32, (ks * 16 + hi * 8) * 2, KT_RS));
-        dq_acc[dt] = mfma32_bf16(pa, bf, dq_acc[dt]);
-      }
-    }
-    __syncthreads();
+      for (int dt = 0; dt < NDT; ++dt) ka[dt] = boff + tr_a[kp][dt];
+      fa_tr_read<D, ks * 16 * D * 2>(bf, ka);
+#pragma unroll
+      for (int dt = 0; dt < NDT; ++dt) dq_acc[dt] = mfma32_bf16(pa, bf[dt], dq_acc[dt]);
+    };
+    dq_step(std::integral_constant<int, 0>{});
+    dq_step(std::integral_constant<int, 1>{});
+    dq_step(std::integral_constant<int, 2>{});
+    dq_step(std::integral_constant<int, 3>{});
   }
 
   // ---- epilogue -----------------------------------------------------------

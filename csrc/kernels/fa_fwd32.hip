@@ -16,8 +16,17 @@
 //   * P stays in registers: the PV A-fragments are assembled with packed
 //     bf16 pairs + 2x permlane32_swap per k-step -- no P LDS round-trip,
 //     no lgkmcnt(0) stall.
-//   * K staged via async global_load_lds with pre-swizzled source;
-//     V^T staged with bank-rotated scalar writes.
+//   * K and V land once per tile, by async global_load_lds with a
+//     pre-swizzled source column, in their natural [64 kv][D] image
+//     (fa_common.h, fa_kv_off).  K feeds S^T by ds_read_b128 rows; V feeds
+//     P V by ds_read_b64_tr_b16, so no transposed copy of V is built and
+//     no VGPR-destination load is left in the loop of full tiles.  Two
+//     {K, V} buffers, tile t+1 in flight under tile t's math, one barrier
+//     per tile.  Every MFMA gets the operands, in the k order, of the
+//     kernel this replaces (V^T by scalar writes), so O and LSE are
+//     bit-identical to it.  Measured, B12 H32 S2048 D128 causal: 1366 ->
+//     664 us per call in the flagship trace, SQ_LDS_BANK_CONFLICT 1.6e8 ->
+//     0, 234 -> 210 VGPR (docs/KERNELS.md, "forward and dQ").
 //   * defer-max rescale, boundary-only masking.
 //   * LSE saved (fp32) for backward + ring/context-parallel merges.
 #include "fa_common.h"
@@ -46,11 +55,11 @@ __global__ void fa_fwd32_kernel(const FaArgs a) {
   constexpr int KB = 64;           // kv tile
   constexpr int NKS = D / 16;      // q/k k-steps over head dim (mfma K=16)
   constexpr int NDT = D / 32;      // output d tiles (32 wide)
-  constexpr unsigned K_RS = D * 2;
-  constexpr unsigned VT_RS = KB * 2;
-  // double-buffered: stage tile t+1 while the MFMAs chew tile t
-  __shared__ char k_lds[2][KB * D * 2];
-  __shared__ char vt_lds[2][D * KB * 2];
+  constexpr int TILE = KB * D * 2;  // bytes of one [64][D] tile
+  // one array (a second __shared__ object beside a DMA target can cost a
+  // vmcnt(0) per LDS read): two {K, V} buffers, tile t+1 in flight while the
+  // MFMAs chew tile t
+  __shared__ __attribute__((aligned(16))) char lds[4 * TILE];
 
   // block index on the SLOW grid dim (y) so causal longest-first ordering
   // is global: the dispatcher walks x fastest, so a length-ordered y makes
@@ -100,62 +109,29 @@ __global__ void fa_fwd32_kernel(const FaArgs a) {
 
   const int kv_end = CAUSAL ? min(Skv_e, q0 + QB + cdelta) : Skv_e;
 
-  // K-staging source offsets (pre-swizzled so async DMA lands swizzled rows)
-  constexpr unsigned KSWZ = (D >= 128) ? 15u : 7u;
-  int k_row[KB * D / (NT * 8)], k_colp[KB * D / (NT * 8)];
+  // LDS addresses of the lane's rows for the transposed reads of V
+  const unsigned lds_a = (unsigned)(size_t)(__attribute__((address_space(3))) char*)lds;
+  unsigned tr_a[2][NDT];   // even, odd k-steps
 #pragma unroll
-  for (int it = 0; it < KB * D / (NT * 8); ++it) {
-    int flat = it * NT * 8 + tid * 8;
-    int row = flat / D, col = flat % D;
-    k_row[it] = row;
-    k_colp[it] = col ^ ((row & (int)KSWZ) << 3);
+  for (int dt = 0; dt < NDT; ++dt) {
+    tr_a[0][dt] = fa_tr_addr<D>(lds_a, lane, dt, 0);
+    tr_a[1][dt] = fa_tr_addr<D>(lds_a, lane, dt, 16);
   }
 
-  auto stage = [&](int buf, int kv0) {
-    // ---- stage K [KB][D] (async, swizzled) + V^T [D][KB] ------------------
-    if (kv0 + KB <= Skv_e) {
-#pragma unroll
-      for (int it = 0; it < KB * D / (NT * 8); ++it) {
-        const short* src = kg + kbase + (long long)(kv0 + k_row[it]) * k_ss + k_colp[it];
-        char* dst = k_lds[buf] + it * NT * 16 + (tid >> 6) * 64 * 16;
-        __builtin_amdgcn_global_load_lds(
-            (const __attribute__((address_space(1))) unsigned int*)src,
-            (__attribute__((address_space(3))) unsigned int*)dst, 16, 0, 0);
-      }
-    } else {
-      for (int flat = tid * 8; flat < KB * D; flat += NT * 8) {
-        int row = flat / D, col = flat % D;
-        shortx8 val;
-        if (kv0 + row < Skv_e)
-          val = *reinterpret_cast<const shortx8*>(kg + kbase + (long long)(kv0 + row) * k_ss + col);
-        else
-          for (int i = 0; i < 8; ++i) val[i] = 0;
-        *reinterpret_cast<shortx8*>(k_lds[buf] + lds_off32w(row, col * 2, K_RS, KSWZ)) = val;
-      }
-    }
-    {
-      const int rot = tid & 7;
-      for (int flat = tid * 8; flat < KB * D; flat += NT * 8) {
-        int row = flat / D, col = flat % D;  // row=kv, col=d
-        shortx8 val;
-        if (kv0 + row < Skv_e)
-          val = *reinterpret_cast<const shortx8*>(vg + kbase + (long long)(kv0 + row) * k_ss + col);
-        else
-          for (int i = 0; i < 8; ++i) val[i] = 0;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          int i = (j + rot) & 7;
-          *reinterpret_cast<short*>(vt_lds[buf] + lds_off32(col + i, row * 2, VT_RS)) = val[i];
-        }
-      }
-    }
-  };
-
-  stage(0, 0);
-  __syncthreads();
+  if (kv_end > 0) fa_stage_kv<D, NT>(lds, kg, vg, kbase, k_ss, 0, Skv_e, tid);
   int cur = 0;
   for (int kv0 = 0; kv0 < kv_end; kv0 += KB) {
-    if (kv0 + KB < kv_end) stage(cur ^ 1, kv0 + KB);
+    // Tile kv0 was issued one tile ago (or in the prologue) and nothing newer
+    // is in flight, so the counted wait is vmcnt(0).  The one barrier per
+    // tile says both "tile kv0 has landed for every wave" and "every wave is
+    // done reading tile kv0-KB", which frees the other buffer.
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    const unsigned boff = cur * (2 * TILE);
+    const char* k_t = lds + boff;
+    if (kv0 + KB < kv_end)
+      fa_stage_kv<D, NT>(lds + (cur ^ 1) * (2 * TILE), kg, vg, kbase, k_ss, kv0 + KB, Skv_e, tid);
+    cur ^= 1;
 
     // ---- S^T = K Q^T : 2 kv tiles of 32 -----------------------------------
     floatx16 st[2];
@@ -166,7 +142,7 @@ __global__ void fa_fwd32_kernel(const FaArgs a) {
 #pragma unroll
       for (int ks = 0; ks < NKS; ++ks) {
         shortx8 kf = *reinterpret_cast<const shortx8*>(
-            k_lds[cur] + lds_off32w(t * 32 + l32, (ks * 16 + hi * 8) * 2, K_RS, KSWZ));
+            k_t + fa_kv_off<D>(t * 32 + l32, ks * 2 + hi));
         st[t] = mfma32_bf16(kf, qf[ks], st[t]);
       }
     }
@@ -265,10 +241,12 @@ __global__ void fa_fwd32_kernel(const FaArgs a) {
     }
 
     // ---- O += P V : assemble P A-frags in-register ------------------------
-#pragma unroll
-    for (int ks = 0; ks < KB / 16; ++ks) {
-      const int t = ks >> 1;
-      const int kp = ks & 1;
+    // one k-step of 16 kv rows; KS is a type so the offsets of the
+    // transposed reads are immediates
+    auto pv_step = [&](auto KS) {
+      constexpr int ks = decltype(KS)::value;
+      constexpr int t = ks >> 1;
+      constexpr int kp = ks & 1;
       // STATIC register indices only (rule #20: a runtime `hi` index into
       // the v16 accumulator becomes a 16-way cndmask tree); pack all four
       // candidate words, then one select each by hi.
@@ -293,15 +271,19 @@ __global__ void fa_fwd32_kernel(const FaArgs a) {
       paw[2] = hi ? O1 : X1;
       paw[3] = hi ? O2 : X2;
       shortx8 pa = *reinterpret_cast<shortx8*>(&paw);
+      // B[k = 16*ks + 8*hi + 0..7][n = 32*dt + l32] of V, by transposed reads
+      shortx8 vf[NDT];
+      unsigned va[NDT];
 #pragma unroll
-      for (int dt = 0; dt < NDT; ++dt) {
-        shortx8 vf = *reinterpret_cast<const shortx8*>(
-            vt_lds[cur] + lds_off32(dt * 32 + l32, (ks * 16 + hi * 8) * 2, VT_RS));
-        oacc[dt] = mfma32_bf16(pa, vf, oacc[dt]);
-      }
-    }
-    __syncthreads();
-    cur ^= 1;
+      for (int dt = 0; dt < NDT; ++dt) va[dt] = boff + tr_a[kp][dt];
+      fa_tr_read<D, TILE + ks * 16 * D * 2>(vf, va);
+#pragma unroll
+      for (int dt = 0; dt < NDT; ++dt) oacc[dt] = mfma32_bf16(pa, vf[dt], oacc[dt]);
+    };
+    pv_step(std::integral_constant<int, 0>{});
+    pv_step(std::integral_constant<int, 1>{});
+    pv_step(std::integral_constant<int, 2>{});
+    pv_step(std::integral_constant<int, 3>{});
   }
 
   // ---- epilogue: O /= l, store O + LSE ------------------------------------
