@@ -446,6 +446,26 @@ static bool fa_same(const pa::FaStride& x, const pa::FaStride& y) {
   return x.b == y.b && x.h == y.h && x.s == y.s;
 }
 
+// GQA backward: G = gqa_heads_per_block q heads per dK/dV block (0 = the whole
+// group of h / hkv).  Below the group size the blocks write fp32 partials,
+// which this allocates; the returned tensor must outlive the launch.
+static Tensor fa_gqa_setup(pa::FaArgs& a, int64_t gqa_heads_per_block, const Tensor& like) {
+  const int64_t rep = a.h / a.hkv;
+  TORCH_CHECK(gqa_heads_per_block >= 0 &&
+              (gqa_heads_per_block == 0 || rep % gqa_heads_per_block == 0),
+              "flash_attn_bwd: gqa_heads_per_block must be 0 or divide H / HKV (", rep, ")");
+  TORCH_CHECK(a.hkv == a.h || a.mask == nullptr,
+              "flash_attn_bwd: hkv != h with a mask has no kernel (expand KV upstream)");
+  a.gqa_heads = (int)gqa_heads_per_block;
+  Tensor ws;
+  if (a.gqa_heads != 0 && a.gqa_heads != rep) {
+    ws = torch::empty({2, (int64_t)a.b * (a.h / a.gqa_heads), a.skv, a.dh},
+                      like.options().dtype(torch::kFloat));
+    a.gqa_ws = ws.mutable_data_ptr<float>();
+  }
+  return ws;
+}
+
 static pa::FaStride fa_mask_strides(const Tensor& m, int64_t b, int64_t h,
                                     int64_t sq, int64_t skv) {
   TORCH_CHECK(m.dim() == 4 && m.size(3) == skv && m.size(2) == sq &&
@@ -506,9 +526,9 @@ std::vector<Tensor> flash_attn_bwd(const Tensor& dout, const Tensor& q, const Te
                                    c10::optional<Tensor> dv_out,
                                    double scale, bool causal,
                                    c10::optional<Tensor> mask,
-                                   double pdrop, int64_t seed, int64_t offset) {
+                                   double pdrop, int64_t seed, int64_t offset,
+                                   int64_t gqa_heads_per_block) {
   pa::FaArgs a = fa_dense_args(q, k, v, scale, causal, mask, pdrop, seed, offset);
-  TORCH_CHECK(a.hkv == a.h, "flash_attn_bwd kernel requires hkv==h (expand KV upstream)");
   auto dq = dq_out.has_value() ? *dq_out : torch::empty({a.b, a.h, a.sq, a.dh}, q.options());
   auto dk = dk_out.has_value() ? *dk_out : torch::empty({a.b, a.hkv, a.skv, a.dh}, k.options());
   auto dv = dv_out.has_value() ? *dv_out : torch::empty({a.b, a.hkv, a.skv, a.dh}, v.options());
@@ -530,6 +550,7 @@ std::vector<Tensor> flash_attn_bwd(const Tensor& dout, const Tensor& q, const Te
   a.lse = const_cast<float*>(lse.const_data_ptr<float>());
   a.delta = delta.mutable_data_ptr<float>();
   a.dq = dq.mutable_data_ptr(); a.dk = dk.mutable_data_ptr(); a.dv = dv.mutable_data_ptr();
+  Tensor ws = fa_gqa_setup(a, gqa_heads_per_block, q);
   pa::flash_attn_bwd(a, cur_stream());
   return {dq, dk, dv};
 }
@@ -591,9 +612,8 @@ static pa::FaArgs fa_varlen_args(const Tensor& q, const Tensor& k, const Tensor&
   TORCH_CHECK(a.dh == 128 || a.dh == 64, "flash_attn_varlen: head_dim must be 64/128");
   TORCH_CHECK(k.size(2) == a.dh && v.sizes() == k.sizes(),
               "flash_attn_varlen: k and v must be [total_k, HKV, D] with q's D");
-  TORCH_CHECK(bwd ? a.hkv == a.h : (a.hkv > 0 && a.h % a.hkv == 0),
-              bwd ? "flash_attn_varlen_bwd requires hkv == h"
-                  : "flash_attn_varlen: H must be a multiple of HKV");
+  TORCH_CHECK(a.hkv > 0 && a.h % a.hkv == 0,
+              "flash_attn_varlen: H must be a multiple of HKV");
   TORCH_CHECK(cu_q.scalar_type() == torch::kInt32 && cu_k.scalar_type() == torch::kInt32 &&
               cu_q.dim() == 1 && cu_k.dim() == 1 && cu_q.size(0) == cu_k.size(0) &&
               cu_q.size(0) >= 2,
@@ -647,7 +667,8 @@ std::vector<Tensor> flash_attn_varlen_bwd(const Tensor& dout, const Tensor& q,
                                           const Tensor& cu_q, const Tensor& cu_k,
                                           double scale, bool causal,
                                           double pdrop, int64_t seed,
-                                          int64_t offset) {
+                                          int64_t offset,
+                                          int64_t gqa_heads_per_block) {
   std::vector<Tensor> keep;
   pa::FaArgs a = fa_varlen_args(q, k, v, cu_q, cu_k, scale, causal, pdrop, seed, offset,
                                 true, keep);
@@ -668,6 +689,7 @@ std::vector<Tensor> flash_attn_varlen_bwd(const Tensor& dout, const Tensor& q,
   a.lse = const_cast<float*>(lse.const_data_ptr<float>());
   a.delta = delta.mutable_data_ptr<float>();
   a.dq = dq.mutable_data_ptr(); a.dk = dk.mutable_data_ptr(); a.dv = dv.mutable_data_ptr();
+  Tensor ws = fa_gqa_setup(a, gqa_heads_per_block, q);
   pa::flash_attn_bwd(a, cur_stream());
   return {dq, dk, dv};
 }
@@ -1493,13 +1515,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("k"), py::arg("v"), py::arg("cu_q"), py::arg("cu_k"),
         py::arg("scale"), py::arg("causal"), py::arg("pdrop") = 0.0,
         py::arg("seed") = 0, py::arg("offset") = 0);
-  m.def("flash_attn_varlen_bwd", &flash_attn_varlen_bwd);
+  m.def("flash_attn_varlen_bwd", &flash_attn_varlen_bwd, py::arg("dout"),
+        py::arg("q"), py::arg("k"), py::arg("v"), py::arg("o"), py::arg("lse"),
+        py::arg("cu_q"), py::arg("cu_k"), py::arg("scale"), py::arg("causal"),
+        py::arg("pdrop"), py::arg("seed"), py::arg("offset"),
+        py::arg("gqa_heads_per_block") = 0);
   m.def("flash_attn_bwd", &flash_attn_bwd, py::arg("dout"), py::arg("q"),
         py::arg("k"), py::arg("v"), py::arg("o"), py::arg("lse"),
         py::arg("dq") = c10::nullopt, py::arg("dk") = c10::nullopt,
         py::arg("dv") = c10::nullopt, py::arg("scale"), py::arg("causal"),
         py::arg("mask") = c10::nullopt, py::arg("pdrop") = 0.0,
-        py::arg("seed") = 0, py::arg("offset") = 0);
+        py::arg("seed") = 0, py::arg("offset") = 0,
+        py::arg("gqa_heads_per_block") = 0);
   m.def("dropout_add_fwd", &dropout_add_fwd);
   m.def("dropout_add_bwd", &dropout_add_bwd);
   m.def("embedding_fwd", &embedding_fwd);

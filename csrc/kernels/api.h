@@ -122,7 +122,11 @@ void l2norm_sq(const void* x, float* out, int64_t numel, int dtype,
 // packed totals, strides {0, dh, h * dh}; cu_q / cu_k int32 [nseq + 1] prefix
 // sums; q_bmap / kv_bmap int32 (seq, row-within-seq) pairs, one per 128-row
 // block; lse / delta [h, total_q]; causal is bottom-right aligned; no mask.
-// The backward needs hkv == h.
+// GQA: h a multiple of hkv, q head i reads K/V head i / (h / hkv); k, v, dk
+// and dv have hkv heads.  The backward takes hkv != h without a mask only.
+// gqa_heads: q heads per dK/dV block, a divisor of h / hkv, 0 = the whole
+// group; below h / hkv the blocks write fp32 partials to gqa_ws, 2 * b *
+// (h / gqa_heads) * skv * dh floats (dK, then dV), which a reduce kernel sums.
 struct FaStride { long long b, h, s; };
 struct FaArgs {
   const void *q, *k, *v;
@@ -140,6 +144,8 @@ struct FaArgs {
   unsigned long long seed, offset;
   const int *cu_q, *cu_k, *q_bmap, *kv_bmap;
   int n_qblocks, n_kvblocks;
+  int gqa_heads;        // backward
+  float* gqa_ws;        // backward workspace, null unless gqa_heads < h / hkv
 };
 void flash_attn_fwd(const FaArgs& a, hipStream_t s);
 // delta = rowsum(dout * o), then dK / dV and dQ

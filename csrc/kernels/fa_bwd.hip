@@ -1,6 +1,7 @@
 // FlashAttention-2 backward for gfx950 (CDNA4): bf16, head_dim 64 / 128,
-// causal or full, hkv == h (the Python layer repeats KV for GQA), dense or
-// varlen.  The forward is in fa_fwd32.hip, the shared pieces in fa_common.h.
+// causal or full, dense or varlen, h a multiple of hkv (GQA: q head h reads
+// K/V head h / (h/hkv), as in the forward).  The forward is in fa_fwd32.hip,
+// the shared pieces in fa_common.h.
 //
 // No atomics; S is recomputed from Q, K and the saved LSE per FA2.  Kernels:
 //   * fa_bwd_delta_kernel: delta[row] = sum_d dO * O.
@@ -14,6 +15,14 @@
 //   * fa_bwd_dq32_kernel: dQ for every path.  MFMA 32x32x16, 4 waves, the
 //     forward's swapped layout and its double-buffered K / V image, K read
 //     by rows and by columns.
+// GQA (hkv != h, no mask) is a compile-time flavour of the three MFMA kernels;
+// the GQA = false instantiations are the hkv == h kernels unchanged.  A dK/dV
+// block owns a kv block of ONE kv head and G consecutive q heads of its group
+// and streams their q tiles, head after head, past the same K/V fragments and
+// the same fp32 accumulators: one K/V read, one fp32 sum, one rounding.
+// G == h/hkv writes bf16 dK/dV; G < h/hkv (more blocks for small grids) writes
+// fp32 partials [b, h/G, skv, d] that fa_bwd_gqa_reduce_kernel sums in fixed
+// order.  No atomics.  hkv != h with a mask is refused by the binding.
 #include "fa_common.h"
 
 namespace pa {
@@ -216,7 +225,12 @@ __device__ __forceinline__ void dkv_mma_tr(floatx4* acc, shortx8 a, const unsign
   }
 }
 
-template <int D, bool CAUSAL>
+// GQA: grid.x = b * hkv * (rep / G); the block streams tiles q_start..Sq of q
+// head h0, then of h0 + 1, ... h0 + G - 1 through the same two buffers: the
+// pipeline is not drained at a head boundary and the buffer parity runs on;
+// q0 wraps to q_start and the q / dO / lse bases advance by one head.  rep, G
+// and ws are read by the GQA instantiations only.
+template <int D, bool CAUSAL, bool GQA>
 __launch_bounds__(512)
 __global__ void fa_bwd_dkv_kernel(const short* __restrict__ dog, const short* __restrict__ qg,
                                   const short* __restrict__ kg, const short* __restrict__ vg,
@@ -226,7 +240,8 @@ __global__ void fa_bwd_dkv_kernel(const short* __restrict__ dog, const short* __
                                   long long q_sb, long long q_sh, long long q_ss,
                                   long long k_sb, long long k_sh, long long k_ss,
                                   long long do_sb, long long do_sh, long long do_ss,
-                                  long long dk_sb, long long dk_sh, long long dk_ss) {
+                                  long long dk_sb, long long dk_sh, long long dk_ss,
+                                  int rep, int G, float* __restrict__ ws) {
   constexpr int NW = 8;               // waves; block owns NW*16 kv rows
   constexpr int NT = NW * 64;
   constexpr int KVEXT = NW * 16;
@@ -243,12 +258,21 @@ __global__ void fa_bwd_dkv_kernel(const short* __restrict__ dog, const short* __
   const int kvblk = blockIdx.y;     // slow dim; kv0=0 (longest) first
   const int bh = blockIdx.x;
   const int kv0 = kvblk * KVEXT;
-  const int b = bh / H, h = bh % H;
-  const long long qbase = (long long)b * q_sb + (long long)h * q_sh;
-  const long long dobase = (long long)b * do_sb + (long long)h * do_sh;
-  const long long kvbase = (long long)b * k_sb + (long long)h * k_sh;
-  const long long dkbase = (long long)b * dk_sb + (long long)h * dk_sh;
-  const long long lse_base = ((long long)bh) * Sq;
+  int b = bh / H, h = bh % H;       // h: first q head of the stream
+  int hk = h;                       // kv head
+  if constexpr (GQA) {
+    const int parts = rep / G, bk = bh / parts, hkv = H / rep;
+    b = bk / hkv; hk = bk % hkv;
+    h = hk * rep + (bh % parts) * G;
+  }
+  // q, dO and lse / delta bases of the tile that is staged next
+  long long qbase = (long long)b * q_sb + (long long)h * q_sh;
+  long long dobase = (long long)b * do_sb + (long long)h * do_sh;
+  const long long kvbase = (long long)b * k_sb + (long long)hk * k_sh;
+  const long long dkbase = (long long)b * dk_sb + (long long)hk * dk_sh;
+  // GQA = false keeps bh * Sq: (b * H + h) * Sq is equal but reorders the
+  // scalar prologue of the hkv == h kernel
+  long long lse_base = GQA ? ((long long)b * H + h) * Sq : ((long long)bh) * Sq;
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -352,11 +376,12 @@ __global__ void fa_bwd_dkv_kernel(const short* __restrict__ dog, const short* __
     load_stats(q_start, lse_n, delta_n);
   }
   int cur = 0;
-  for (int q0 = q_start; q0 < Sq; q0 += QB) {
+  int hleft = GQA ? G - 1 : 0;      // q heads of the stream after the staged one
+  for (int q0 = q_start, qn; q0 < Sq; q0 = qn) {
     // Tile q0 was issued one tile ago (or in the prologue) and nothing newer
     // is in flight, so the counted wait is vmcnt(0).  The one barrier per
     // tile then says both "tile q0 has landed for every wave" and "every
-    // wave is done reading tile q0-QB", which frees the other buffer.
+    // wave is done reading the tile before", which frees the other buffer.
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     const unsigned boff = cur * (2 * TILE);
@@ -364,9 +389,17 @@ __global__ void fa_bwd_dkv_kernel(const short* __restrict__ dog, const short* __
     float lse_v[4], delta_v[4];
 #pragma unroll
     for (int nt = 0; nt < 4; ++nt) { lse_v[nt] = lse_n[nt]; delta_v[nt] = delta_n[nt]; }
-    if (q0 + QB < Sq) {
-      stage(q0 + QB, lds + (cur ^ 1) * (2 * TILE));
-      load_stats(q0 + QB, lse_n, delta_n);
+    qn = q0 + QB;
+    if constexpr (GQA) {
+      if (qn >= Sq && hleft > 0) {   // head boundary: the next head's first tile
+        --hleft;
+        qn = q_start;
+        qbase += q_sh; dobase += do_sh; lse_base += Sq;
+      }
+    }
+    if (qn < Sq) {
+      stage(qn, lds + (cur ^ 1) * (2 * TILE));
+      load_stats(qn, lse_n, delta_n);
     }
     cur ^= 1;
     const char* do_t = q_t + TILE;
@@ -441,6 +474,23 @@ __global__ void fa_bwd_dkv_kernel(const short* __restrict__ dog, const short* __
   }
 
   // write dK, dV
+  if constexpr (GQA) {
+    if (G != rep) {   // fp32 partials [grid.x, Skv, D]: dK, then dV
+      float* wk = ws + (long long)bh * Skv * D;
+      float* wv = wk + (long long)gridDim.x * Skv * D;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        int row = kv0 + wq * 16 + lg * 4 + r;
+        if (row >= Skv) continue;
+#pragma unroll
+        for (int dt = 0; dt < NDT; ++dt) {
+          wk[(long long)row * D + dt * 16 + l16] = dk_acc[dt][r];
+          wv[(long long)row * D + dt * 16 + l16] = dv_acc[dt][r];
+        }
+      }
+      return;
+    }
+  }
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     int row = kv0 + wq * 16 + lg * 4 + r;
@@ -469,7 +519,9 @@ __global__ void fa_bwd_dkv_kernel(const short* __restrict__ dog, const short* __
 // flagship trace, SQ_LDS_BANK_CONFLICT 1.4e8 -> 0, 256 VGPR + 12 B scratch ->
 // 248 VGPR and none (docs/KERNELS.md, "forward and dQ").
 // ---------------------------------------------------------------------------
-template <int D, bool CAUSAL, bool MASKED, bool DROPOUT, bool VARLEN>
+// GQA: K / V come from head h / rep (the forward's head map); rep is read
+// by the GQA instantiations only.
+template <int D, bool CAUSAL, bool MASKED, bool DROPOUT, bool VARLEN, bool GQA>
 __launch_bounds__(256, 2)
 __global__ void fa_bwd_dq32_kernel(const short* __restrict__ dog, const short* __restrict__ qg,
                                    const short* __restrict__ kg, const short* __restrict__ vg,
@@ -486,7 +538,7 @@ __global__ void fa_bwd_dq32_kernel(const short* __restrict__ dog, const short* _
                                    unsigned long long roffset,
                                    const int* __restrict__ cu_q,
                                    const int* __restrict__ cu_k,
-                                   const int* __restrict__ bmap) {
+                                   const int* __restrict__ bmap, int rep) {
   constexpr int NW = 4;
   constexpr int NT = NW * 64;
   constexpr int QB = NW * 32;       // 128 q rows / block
@@ -514,13 +566,13 @@ __global__ void fa_bwd_dq32_kernel(const short* __restrict__ dog, const short* _
     qbase = (long long)qs0 * q_ss + (long long)h * q_sh;
     dobase = (long long)qs0 * do_ss + (long long)h * do_sh;
     dqbase = (long long)qs0 * dq_ss + (long long)h * dq_sh;
-    kvbase = (long long)ks0 * k_ss + (long long)h * k_sh;
+    kvbase = (long long)ks0 * k_ss + (long long)(GQA ? h / rep : h) * k_sh;
   } else {
     q0 = (CAUSAL ? ((int)gridDim.y - 1 - qblk) : qblk) * QB;   // longest-first
     qbase = (long long)b * q_sb + (long long)h * q_sh;
     dobase = (long long)b * do_sb + (long long)h * do_sh;
     dqbase = (long long)b * dq_sb + (long long)h * dq_sh;
-    kvbase = (long long)b * k_sb + (long long)h * k_sh;
+    kvbase = (long long)b * k_sb + (long long)(GQA ? h / rep : h) * k_sh;
   }
   const long long lse_base = ((long long)bh) * Sq + qglob0;
 
@@ -724,7 +776,11 @@ __global__ void fa_bwd_dq32_kernel(const short* __restrict__ dog, const short* _
 // Keeps its scalar arguments and its own prologue: its mask + dropout dK
 // instantiations sit at the 256-VGPR limit, and with FaArgs and fa_block
 // their scratch size moves by a few bytes.
-template <int D, bool CAUSAL, bool IS_DK, bool MASKED, bool DROPOUT, bool VARLEN>
+// GQA: as fa_bwd_dkv_kernel, grid.x = b * hkv * (rep / G) and one tile stream
+// over the G q heads of the block; the dropout element index follows the q
+// head of the tile.  rep, G and ws (this launch's fp32 partials
+// [grid.x, Skv, D]) are read by the GQA instantiations only.
+template <int D, bool CAUSAL, bool IS_DK, bool MASKED, bool DROPOUT, bool VARLEN, bool GQA>
 __launch_bounds__(256, 2)
 __global__ void fa_bwd_dkv32_kernel(const short* __restrict__ dog, const short* __restrict__ qg,
                                     const short* __restrict__ kg, const short* __restrict__ vg,
@@ -741,7 +797,8 @@ __global__ void fa_bwd_dkv32_kernel(const short* __restrict__ dog, const short* 
                                     unsigned long long roffset,
                                     const int* __restrict__ cu_q,
                                     const int* __restrict__ cu_k,
-                                    const int* __restrict__ bmap) {
+                                    const int* __restrict__ bmap,
+                                    int rep, int G, float* __restrict__ ws) {
   constexpr int NW = 4;
   constexpr int NT = NW * 64;
   constexpr int KVB = NW * 32;     // 128 kv rows / block
@@ -756,11 +813,17 @@ __global__ void fa_bwd_dkv32_kernel(const short* __restrict__ dog, const short* 
 
   const int kvblk = blockIdx.y;     // slow dim; kv0=0 (longest) dispatches first
   const int bh = blockIdx.x;
-  int b = bh / H, h = bh % H;
-  int kv0, Sq_e = Sq, Skv_e = Skv, cdelta = 0, qglob0 = 0;
-  long long qbase, dobase, kvbase, outbase;
+  int b = bh / H, h = bh % H;       // h: q head of the current tile
+  int hk = h;                       // kv head
+  if constexpr (GQA) {              // varlen: b = 0 and H = h, so one map serves both
+    const int parts = rep / G, bk = bh / parts, hkv = H / rep;
+    b = bk / hkv; hk = bk % hkv;
+    h = hk * rep + (bh % parts) * G;
+  }
+  int kv0, Sq_e = Sq, Skv_e = Skv, cdelta = 0, qglob0 = 0, kglob0 = 0;
+  long long qbase_c, dobase_c, kvbase, outbase;   // _c: of the current tile's head
   if (VARLEN) {
-    b = 0; h = bh;
+    if constexpr (!GQA) { b = 0; h = bh; hk = h; }
     const int seq = bmap[2 * kvblk];
     kv0 = bmap[2 * kvblk + 1];
     const int qs0 = cu_q[seq], ks0 = cu_k[seq];
@@ -768,18 +831,20 @@ __global__ void fa_bwd_dkv32_kernel(const short* __restrict__ dog, const short* 
     Skv_e = cu_k[seq + 1] - ks0;
     cdelta = Skv_e - Sq_e;
     qglob0 = qs0;
-    qbase = (long long)qs0 * q_ss + (long long)h * q_sh;
-    dobase = (long long)qs0 * do_ss + (long long)h * do_sh;
-    kvbase = (long long)ks0 * k_ss + (long long)h * k_sh;
-    outbase = (long long)ks0 * dk_ss + (long long)h * dk_sh;
+    kglob0 = ks0;
+    qbase_c = (long long)qs0 * q_ss + (long long)h * q_sh;
+    dobase_c = (long long)qs0 * do_ss + (long long)h * do_sh;
+    kvbase = (long long)ks0 * k_ss + (long long)hk * k_sh;
+    outbase = (long long)ks0 * dk_ss + (long long)hk * dk_sh;
   } else {
     kv0 = kvblk * KVB;
-    qbase = (long long)b * q_sb + (long long)h * q_sh;
-    dobase = (long long)b * do_sb + (long long)h * do_sh;
-    kvbase = (long long)b * k_sb + (long long)h * k_sh;
-    outbase = (long long)b * dk_sb + (long long)h * dk_sh;
+    qbase_c = (long long)b * q_sb + (long long)h * q_sh;
+    dobase_c = (long long)b * do_sb + (long long)h * do_sh;
+    kvbase = (long long)b * k_sb + (long long)hk * k_sh;
+    outbase = (long long)b * dk_sb + (long long)hk * dk_sh;
   }
-  const long long lse_base = ((long long)bh) * Sq + qglob0;
+  long long lse_base_c = GQA ? ((long long)b * H + h) * Sq + qglob0
+                           : ((long long)bh) * Sq + qglob0;
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -813,8 +878,12 @@ __global__ void fa_bwd_dkv32_kernel(const short* __restrict__ dog, const short* 
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[dt][r] = 0.f;
 
-  // stage the transposed operand tile (rotated scalar writes) + stats
-  auto stage = [&](int buf, int q0) {
+  // stage the transposed operand tile (rotated scalar writes) + stats of
+  // the head `hadv` (0 or 1) after the current one
+  auto stage = [&](int buf, int q0, int hadv) {
+    const long long lse_base = lse_base_c + (GQA ? (long long)hadv * Sq : 0);
+    const long long qbase = qbase_c + (GQA ? hadv * q_sh : 0);
+    const long long dobase = dobase_c + (GQA ? hadv * do_sh : 0);
     if (tid < QT) {
       int qa = q0 + tid;
       stat_s[buf][tid] = (qa < Sq_e) ? lseg[lse_base + qa] : 1e30f;
@@ -842,11 +911,22 @@ __global__ void fa_bwd_dkv32_kernel(const short* __restrict__ dog, const short* 
   };
 
   const int q_start = CAUSAL ? (max(0, kv0 - cdelta) / QT) * QT : 0;
-  stage(0, q_start);
+  stage(0, q_start, 0);
   __syncthreads();
   int cur = 0;
-  for (int q0 = q_start; q0 < Sq_e; q0 += QT) {
-    if (q0 + QT < Sq_e) stage(cur ^ 1, q0 + QT);
+  int hleft = GQA ? G - 1 : 0;      // q heads of the stream after the current one
+  for (int q0 = q_start, qn; q0 < Sq_e; q0 = qn) {
+    const long long qbase = qbase_c, dobase = dobase_c;
+    qn = q0 + QT;
+    int hadv = 0;
+    if constexpr (GQA) {
+      if (qn >= Sq_e && hleft > 0) {   // head boundary: the next head's first tile
+        --hleft;
+        qn = q_start;
+        hadv = 1;
+      }
+    }
+    if (qn < Sq_e) stage(cur ^ 1, qn, hadv);
 
     // Q (and dO for dK) A-fragments straight from global: lane = q row
     const int q_lane = q0 + l32;
@@ -936,9 +1016,28 @@ __global__ void fa_bwd_dkv32_kernel(const short* __restrict__ dog, const short* 
     }
     __syncthreads();
     cur ^= 1;
+    if constexpr (GQA) {
+      if (hadv) { ++h; qbase_c += q_sh; dobase_c += do_sh; lse_base_c += Sq; }
+    }
   }
 
   // ---- epilogue: transposed accumulators -> natural rows ------------------
+  if constexpr (GQA) {
+    if (G != rep) {   // fp32 partials, 16-byte stores
+      if (kv_lane < Skv_e) {
+        float* wrow = ws + ((long long)bh * Skv + kglob0 + kv_lane) * D;
+#pragma unroll
+        for (int dt = 0; dt < NDT; ++dt)
+#pragma unroll
+          for (int g = 0; g < 4; ++g) {
+            floatx4 pv = {acc[dt][g * 4], acc[dt][g * 4 + 1], acc[dt][g * 4 + 2],
+                          acc[dt][g * 4 + 3]};
+            *reinterpret_cast<floatx4*>(wrow + dt * 32 + 8 * g + 4 * hi) = pv;
+          }
+      }
+      return;
+    }
+  }
   if (kv_lane < Skv_e) {
     const long long orow = outbase + (long long)kv_lane * dk_ss;
 #pragma unroll
@@ -955,11 +1054,45 @@ __global__ void fa_bwd_dkv32_kernel(const short* __restrict__ dog, const short* 
 }
 
 // ---------------------------------------------------------------------------
+// GQA with G < rep: sums the rep/G fp32 partials of each kv head, in the order
+// of the q heads, and writes bf16 dK / dV through dk_s.  ws holds
+// [nbk * parts, Skv, D] for dK, then the same for dV (nbk = b * hkv); n4 is
+// nbk * Skv * D / 4, the 16-byte groups of one output tensor.  Grid-stride,
+// 16-byte loads, 8-byte stores, no atomics: the result depends on nothing
+// but the partials.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void fa_bwd_gqa_reduce_kernel(
+    const float* __restrict__ ws, short* __restrict__ dkg, short* __restrict__ dvg,
+    int hkv, int parts, int Skv, int D4, long long n4,
+    long long dk_sb, long long dk_sh, long long dk_ss) {
+  const floatx4* ws4 = reinterpret_cast<const floatx4*>(ws);
+  const long long pstride = (long long)Skv * D4;   // one partial, in 16-byte groups
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < 2 * n4;
+       i += (long long)gridDim.x * 256) {
+    const bool is_dv = i >= n4;
+    const long long j = is_dv ? i - n4 : i;
+    const int c4 = (int)(j % D4);
+    const int row = (int)((j / D4) % Skv);
+    const long long bk = j / pstride;
+    const floatx4* src = ws4 + (is_dv ? n4 * parts : 0) + (bk * parts) * pstride
+                       + (long long)row * D4 + c4;
+    floatx4 acc = src[0];
+    for (int p = 1; p < parts; ++p) acc += src[p * pstride];
+    const shortx4 o = {f2bf(acc[0]), f2bf(acc[1]), f2bf(acc[2]), f2bf(acc[3])};
+    short* dst = (is_dv ? dvg : dkg) + (bk / hkv) * dk_sb + (bk % hkv) * dk_sh
+               + (long long)row * dk_ss + c4 * 4;
+    *reinterpret_cast<shortx4*>(dst) = o;
+  }
+}
+
+// ---------------------------------------------------------------------------
 // host launcher: delta, then dK / dV, then dQ.  Dense without mask and
 // dropout takes fa_bwd_dkv_kernel for dK / dV; every other path takes
 // fa_bwd_dkv32_kernel, once for dV and once for dK.  The kernels keep scalar
 // arguments (see docs/KERNELS.md, launch path); FA_BWD_ARGS spells them out
-// once, from the named fields of FaArgs.
+// once, from the named fields of FaArgs.  hkv != h picks the GQA
+// instantiations (dense without mask, varlen); their dK/dV grid is
+// b * hkv * (rep / G) wide, and G < rep adds the reduce over a.gqa_ws.
 // ---------------------------------------------------------------------------
 #define FA_BWD_ARGS(OUT_S)                                                      \
   a.b, a.h, a.sq, a.skv, a.scale, a.q_s.b, a.q_s.h, a.q_s.s,                    \
@@ -972,38 +1105,54 @@ __global__ void fa_bwd_dkv32_kernel(const short* __restrict__ dog, const short* 
 void flash_attn_bwd(const FaArgs& a, hipStream_t s) {
   const bool varlen = a.cu_q != nullptr;
   flash_attn_bwd_delta(a.dout, a.o, a.delta, a.b, a.h, a.sq, a.dh, a.do_s, a.o_s, s);
-  const dim3 gkv((unsigned)(a.b * a.h),
+  const int rep = a.h / a.hkv;
+  const int G = a.gqa_heads > 0 ? a.gqa_heads : rep;   // q heads per dK/dV block
+  const dim3 gkv((unsigned)(a.b * (a.h / G)),
                  (unsigned)(varlen ? a.n_kvblocks : cdiv(a.skv, 128)));
   const dim3 gq((unsigned)(a.b * a.h),
                 (unsigned)(varlen ? a.n_qblocks : cdiv(a.sq, 128)));
   const short *dout = (const short*)a.dout, *q = (const short*)a.q;
   const short *k = (const short*)a.k, *v = (const short*)a.v;
   const float *lse = a.lse, *delta = a.delta;
+  // fp32 partials of one output tensor (G < rep only)
+  const long long ws_half = (long long)gkv.x * a.skv * a.dh;
   auto dkv32 = [&](auto dv_kernel, auto dk_kernel) {   // dV, then dK
     hipLaunchKernelGGL(dv_kernel, gkv, dim3(256), 0, s, dout, q, k, v, lse, delta,
-                       (short*)a.dv, FA_BWD_ARGS(dk_s), FA_BWD_TAIL(kv_bmap));
+                       (short*)a.dv, FA_BWD_ARGS(dk_s), FA_BWD_TAIL(kv_bmap),
+                       rep, G, a.gqa_ws + (G != rep ? ws_half : 0));
     hipLaunchKernelGGL(dk_kernel, gkv, dim3(256), 0, s, dout, q, k, v, lse, delta,
-                       (short*)a.dk, FA_BWD_ARGS(dk_s), FA_BWD_TAIL(kv_bmap));
+                       (short*)a.dk, FA_BWD_ARGS(dk_s), FA_BWD_TAIL(kv_bmap),
+                       rep, G, a.gqa_ws);
   };
   auto dq32 = [&](auto kernel) {
     hipLaunchKernelGGL(kernel, gq, dim3(256), 0, s, dout, q, k, v, lse, delta,
-                       (short*)a.dq, FA_BWD_ARGS(dq_s), FA_BWD_TAIL(q_bmap));
+                       (short*)a.dq, FA_BWD_ARGS(dq_s), FA_BWD_TAIL(q_bmap), rep);
   };
-  fa_dispatch(a, [&](auto D, auto C, auto M, auto P) {
-    if (!varlen) {
+  fa_dispatch_gqa(a, [&](auto D, auto C, auto M, auto P, auto Q) {
+    if constexpr (M() && Q()) {
+      // no GQA + mask instantiations: the binding refuses the call
+    } else if (!varlen) {
       if constexpr (!M() && !P())
-        hipLaunchKernelGGL((fa_bwd_dkv_kernel<D(), C()>), gkv, dim3(512), 0, s, dout, q, k, v,
-                           lse, delta, (short*)a.dk, (short*)a.dv, FA_BWD_ARGS(dk_s));
+        hipLaunchKernelGGL((fa_bwd_dkv_kernel<D(), C(), Q()>), gkv, dim3(512), 0, s, dout, q, k,
+                           v, lse, delta, (short*)a.dk, (short*)a.dv, FA_BWD_ARGS(dk_s),
+                           rep, G, a.gqa_ws);
       else
-        dkv32(fa_bwd_dkv32_kernel<D(), C(), false, M(), P(), false>,
-              fa_bwd_dkv32_kernel<D(), C(), true, M(), P(), false>);
-      dq32(fa_bwd_dq32_kernel<D(), C(), M(), P(), false>);
+        dkv32(fa_bwd_dkv32_kernel<D(), C(), false, M(), P(), false, Q()>,
+              fa_bwd_dkv32_kernel<D(), C(), true, M(), P(), false, Q()>);
+      dq32(fa_bwd_dq32_kernel<D(), C(), M(), P(), false, Q()>);
     } else if constexpr (!M()) {   // varlen takes no mask
-      dkv32(fa_bwd_dkv32_kernel<D(), C(), false, false, P(), true>,
-            fa_bwd_dkv32_kernel<D(), C(), true, false, P(), true>);
-      dq32(fa_bwd_dq32_kernel<D(), C(), false, P(), true>);
+      dkv32(fa_bwd_dkv32_kernel<D(), C(), false, false, P(), true, Q()>,
+            fa_bwd_dkv32_kernel<D(), C(), true, false, P(), true, Q()>);
+      dq32(fa_bwd_dq32_kernel<D(), C(), false, P(), true, Q()>);
     }
   });
+  if (G != rep) {
+    const long long n4 = (long long)a.b * a.hkv * a.skv * a.dh / 4;
+    const dim3 gr((unsigned)hmin<long long>(2048LL, (2 * n4 + 255) / 256));
+    hipLaunchKernelGGL(fa_bwd_gqa_reduce_kernel, gr, dim3(256), 0, s, a.gqa_ws,
+                       (short*)a.dk, (short*)a.dv, a.hkv, rep / G, a.skv, a.dh / 4, n4,
+                       a.dk_s.b, a.dk_s.h, a.dk_s.s);
+  }
 }
 #undef FA_BWD_ARGS
 #undef FA_BWD_TAIL

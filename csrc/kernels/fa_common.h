@@ -2,7 +2,8 @@
 // 32x32-MFMA fragment helpers, the per-block geometry of the forward kernel
 // and the runtime -> compile-time dispatch of the launchers.  The forward
 // kernel takes pa::FaArgs (api.h) by value as its one argument; the backward
-// kernels keep scalar arguments (docs/KERNELS.md, launch path).
+// kernels keep scalar arguments (docs/KERNELS.md, launch path), the GQA ones
+// of hkv != h last.
 #pragma once
 #include <type_traits>
 
@@ -230,6 +231,14 @@ inline void fa_dispatch(const FaArgs& a, F&& f) {
         });
       });
     });
+  });
+}
+
+// the backward's dispatch: fa_dispatch plus GQA = (hkv != h)
+template <class F>
+inline void fa_dispatch_gqa(const FaArgs& a, F&& f) {
+  fa_bool(a.hkv != a.h, [&](auto g) {
+    fa_dispatch(a, [&](auto D, auto C, auto M, auto P) { f(D, C, M, P, g); });
   });
 }
 

@@ -686,6 +686,29 @@ def _fa_seed_offset(fixed_seed_offset=None):
     return seed, offset
 
 
+# dK/dV blocks the GQA backward wants before it gives a block more q heads of
+# the group: 256 CUs x occupancy 2.  Measured on MI355X (docs/KERNELS.md, "GQA
+# backward", sweep over every divisor G): B2 H8 HKV1 S4096 D128 causal backward
+# 0.441 ms at 512 blocks (G 1) against 0.545 at 256 (G 2); B4 H32 HKV8 S2048
+# D128 0.692 ms at 512 blocks (G 4) against 0.748 at 1024 and 0.808 at 2048.
+# Any N in (256, 512] picks the fastest G of all three shapes measured; no
+# grid between 256 and 512 blocks was measured.
+_FA_GQA_MIN_BLOCKS = 512
+
+
+def _fa_bwd_gqa_plan(B, H, HKV, n_kv_blocks):
+    """q heads per dK/dV block (gqa_heads_per_block) of the GQA backward: the
+    largest divisor G of rep = H // HKV whose grid B * (H // G) * n_kv_blocks
+    still has _FA_GQA_MIN_BLOCKS blocks, else 1.  G == rep writes bf16 dK/dV
+    straight from the kernel; a smaller G trades an fp32 workspace and a
+    reduce kernel for more blocks.  Shapes only, never data."""
+    rep = max(1, H // HKV)
+    for g in range(rep, 0, -1):
+        if rep % g == 0 and B * (H // g) * n_kv_blocks >= _FA_GQA_MIN_BLOCKS:
+            return g
+    return 1
+
+
 class _FlashAttn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, q, k, v, scale, causal, mask=None, dropout=0.0,
@@ -724,7 +747,14 @@ class _FlashAttn(torch.autograd.Function):
                 do = do.contiguous()
             kw = dict(scale=ctx.scale, causal=ctx.causal, mask=ctx.mask,
                       pdrop=ctx.dropout, seed=ctx.seed, offset=ctx.offset)
-            if k.shape[1] != q.shape[1]:  # GQA: expand for bwd kernel
+            if k.shape[1] != q.shape[1] and ctx.mask is None:
+                # GQA: dK/dV summed per kv head in the kernel
+                g = _fa_bwd_gqa_plan(q.shape[0], q.shape[1], k.shape[1],
+                                     -(-k.shape[2] // 128))
+                dq, dk, dv = C.flash_attn_bwd(do, q, k, v, o, lse, **kw,
+                                              gqa_heads_per_block=g)
+            elif k.shape[1] != q.shape[1]:
+                # GQA with a mask has no kernel: expand K/V, sum the groups
                 rep = q.shape[1] // k.shape[1]
                 ke = k.repeat_interleave(rep, dim=1)
                 ve = v.repeat_interleave(rep, dim=1)
@@ -1706,9 +1736,12 @@ class _FlashAttnVarlen(torch.autograd.Function):
     def backward(ctx, do, _dlse):
         q, k, v, o, lse, cu_q, cu_k = ctx.saved_tensors
         C = _ext.get_ext()
+        # kv blocks from the packed total: a lower bound, no look at cu_k
+        g = _fa_bwd_gqa_plan(1, q.shape[1], k.shape[1], -(-k.shape[0] // 128))
         dq, dk, dv = C.flash_attn_varlen_bwd(do, q, k, v, o, lse, cu_q, cu_k,
                                              ctx.scale, ctx.causal, ctx.dropout,
-                                             ctx.seed, ctx.offset)
+                                             ctx.seed, ctx.offset,
+                                             gqa_heads_per_block=g)
         return dq, dk, dv, None, None, None, None, None, None, None
 
 
@@ -1726,7 +1759,8 @@ def flash_attn_varlen_func(q, k, v, cu_seqlens_q, cu_seqlens_k, max_seqlen_q,
         scale = 1.0 / math.sqrt(q.shape[-1])
     p = dropout if training else 0.0
     if (_ext.use_native(q) and q.dtype == torch.bfloat16
-            and q.shape[-1] in (64, 128) and k.shape[1] == q.shape[1]):
+            and q.shape[-1] in (64, 128) and k.shape[1] > 0
+            and q.shape[1] % k.shape[1] == 0):
         cu_q = cu_seqlens_q.to(torch.int32)
         cu_k = cu_seqlens_k.to(torch.int32)
         seed, offset = _fa_seed_offset() if p > 0 else (0, 0)

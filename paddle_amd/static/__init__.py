@@ -193,7 +193,9 @@ def data(name, shape, dtype="float32", lod_level=0):
 def create_parameter(shape, dtype="float32", initializer=None, program=None):
     prog = program or _default_main
     dt = framework.convert_dtype(dtype)
-    t = torch.empty(shape, dtype=dt)
+    # zeros, not empty: until its initializer runs the tensor must not hold
+    # whatever the allocator left (NaN included)
+    t = torch.zeros(shape, dtype=dt)
     v = Var("param", shape=shape, dtype=dt, tensor=t)
     t.requires_grad_(True)
 
