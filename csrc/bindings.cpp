@@ -374,22 +374,6 @@ Tensor colsum(const Tensor& x) {
   return out;
 }
 
-Tensor weight_only_gemv(const Tensor& x, const Tensor& qweight,
-                        const Tensor& scale, const c10::optional<Tensor>& bias) {
-  CHECK_IN(x); CHECK_IN(qweight); CHECK_IN(scale);
-  TORCH_CHECK(qweight.scalar_type() == torch::kChar, "qweight must be int8");
-  int64_t k = x.size(-1), m = x.numel() / k, n = qweight.size(0);
-  TORCH_CHECK(qweight.size(1) == k && k % 8 == 0);
-  auto sizes = x.sizes().vec();
-  sizes.back() = n;
-  auto out = torch::empty(sizes, x.options());
-  const void* bp = bias.has_value() ? bias->const_data_ptr() : nullptr;
-  pa::weight_only_gemv(x.const_data_ptr(), qweight.const_data_ptr(),
-                       scale.const_data_ptr<float>(), bp,
-                       out.mutable_data_ptr(), m, n, k, dt_of(x), cur_stream());
-  return out;
-}
-
 // ---- adamw ----------------------------------------------------------------
 void adamw(Tensor& master, c10::optional<Tensor> param_out, const Tensor& grad,
            Tensor& m, Tensor& v, double lr, double beta1, double beta2,
@@ -1082,119 +1066,176 @@ Tensor paged_prefill_attention(const Tensor& q, const Tensor& kcache,
   return o;
 }
 
-// ---- hand-written GEMM ----------------------------------------------------
-Tensor gemm_bf16(const Tensor& a, const Tensor& b, bool b_is_nt) {
-  TORCH_CHECK(a.is_cuda() && a.scalar_type() == torch::kBFloat16);
-  TORCH_CHECK(a.dim() == 2 && b.dim() == 2);
-  TORCH_CHECK(a.stride(1) == 1 && b.stride(1) == 1, "row-major inputs only");
-  int64_t m = a.size(0), k = a.size(1);
-  int64_t n = b_is_nt ? b.size(0) : b.size(1);
-  TORCH_CHECK(b_is_nt ? b.size(1) == k : b.size(0) == k);
-  TORCH_CHECK(k % 64 == 0 && k >= 128, "gemm_bf16: K must be multiple of 64");
-  auto c = torch::empty({m, n}, a.options());
-  pa::gemm_bf16(a.const_data_ptr(), b.const_data_ptr(), c.mutable_data_ptr(),
-                m, n, k, a.stride(0), b.stride(0), c.stride(0), b_is_nt,
-                cur_stream());
-  return c;
+static bool aligned16(const Tensor& t) {
+  return reinterpret_cast<uintptr_t>(t.const_data_ptr()) % 16 == 0;
 }
 
-// Full GEMM with layout + fused epilogue.  layout: 0=NT 1=NN 2=TN.
-// epilogue: 0=none 1=bias 2=bias_gelu(aux out) 3=dgelu(aux in).
-// Returns {C} or {C, aux} for bias_gelu.  c_in (optional): accumulate into
-// it in-place (epilogue must be 0) -- the fused_linear_param_grad_add path.
+// ---- dense MFMA GEMM ---------------------------------------------------------
+// Contract of pa::GemmArgs (kernels/api.h, docs/KERNELS.md), shared by
+// gemm_bf16_ex, gemm_bf16_nt_batched, gemm_fp8_nt and gemm_fp8_nt_batched:
+// both operands are staged by 16-byte accesses through their leading
+// dimensions and batch strides, so placement, strides and base alignment are
+// checked here, before any launch.  layout: 0=NT 1=NN 2=TN (fp8: NT).
+// epilogue: 0=none 1=bias 2=bias_gelu(aux out) 3=dgelu(aux in).  c_in:
+// accumulate into it in place (the fused_linear_param_grad_add path).
+// Allocates c (and aux for bias_gelu) and fills the args.
+struct GemmCall {
+  pa::GemmArgs g;
+  Tensor c, aux;
+};
+
+static GemmCall check_gemm(const char* op, bool fp8, bool batched,
+                           const Tensor& a, const Tensor& b, const char* bname,
+                           int64_t layout, int64_t epilogue,
+                           const c10::optional<Tensor>& bias,
+                           const c10::optional<Tensor>& aux_in,
+                           const c10::optional<Tensor>& c_in, double scale_ab) {
+  const int64_t rank = batched ? 3 : 2;
+  const int64_t q = fp8 ? 16 : 8;   // elements per 16 bytes
+  const auto bf16 = torch::kBFloat16;
+  TORCH_CHECK(a.is_cuda(), op, ": a must be a GPU tensor");
+  TORCH_CHECK(b.device() == a.device(), op, ": ", bname, " must be on the device of a");
+  if (fp8) {
+    auto is_f8 = [](const Tensor& t) {
+      return t.scalar_type() == torch::kFloat8_e4m3fn || t.scalar_type() == torch::kUInt8;
+    };
+    TORCH_CHECK(is_f8(a), op, ": a must be float8_e4m3fn or uint8");
+    TORCH_CHECK(is_f8(b), op, ": ", bname, " must be float8_e4m3fn or uint8");
+  } else {
+    TORCH_CHECK(a.scalar_type() == bf16, op, ": a must be bfloat16");
+    TORCH_CHECK(b.scalar_type() == bf16, op, ": ", bname, " must be bfloat16");
+  }
+  TORCH_CHECK(a.dim() == rank && a.stride(-1) == 1, op, ": a must be ", rank,
+              "-D with unit inner stride");
+  TORCH_CHECK(b.dim() == rank && b.stride(-1) == 1, op, ": ", bname,
+              " must be ", rank, "-D with unit inner stride");
+  TORCH_CHECK(layout >= 0 && layout <= 2 && (!fp8 || layout == 0), op,
+              ": layout must be 0 (NT), 1 (NN) or 2 (TN), got ", layout);
+  TORCH_CHECK(epilogue >= 0 && epilogue <= 3, op,
+              ": epilogue must be 0..3, got ", epilogue);
+  const bool a_t = layout == pa::kGemmTN, b_t = layout != pa::kGemmNT;
+  const int64_t m = a.size(a_t ? -1 : -2), k = a.size(a_t ? -2 : -1);
+  const int64_t n = b.size(b_t ? -1 : -2);
+  const int64_t batch = batched ? a.size(0) : 1;
+  TORCH_CHECK(b.size(b_t ? -2 : -1) == k, op, ": inner dims of a and ", bname,
+              " must agree");
+  TORCH_CHECK(!batched || b.size(0) == batch, op, ": a and ", bname,
+              " must have the same batch size");
+  const int64_t kmin = fp8 ? 128 : 64, lim = int64_t(1) << 31;
+  TORCH_CHECK(m >= 1 && n >= 1 && m < lim && n < lim && k < lim, op,
+              ": 1 <= M, N, K < 2^31, got ", m, ", ", n, ", ", k);
+  TORCH_CHECK(k >= kmin, op, ": K must be >= ", kmin, ", got ", k);
+  TORCH_CHECK(batch >= 1 && batch <= 65535, op, ": 1 <= batch <= 65535, got ", batch);
+  auto strides16 = [&](const Tensor& t) {
+    return t.stride(-2) % q == 0 && (!batched || t.stride(0) % q == 0);
+  };
+  TORCH_CHECK(strides16(a), op, ": a row and batch strides must be multiples of ",
+              q, " elements (16 bytes)");
+  TORCH_CHECK(strides16(b), op, ": ", bname,
+              " row and batch strides must be multiples of ", q, " elements (16 bytes)");
+  TORCH_CHECK(aligned16(a), op, ": a data must be 16-byte aligned");
+  TORCH_CHECK(aligned16(b), op, ": ", bname, " data must be 16-byte aligned");
+
+  GemmCall call;
+  pa::GemmArgs& g = call.g;
+  g = pa::GemmArgs{};
+  const bool accumulate = c_in.has_value();
+  if (accumulate) {
+    TORCH_CHECK(epilogue == 0, op, ": accumulate (c_in) requires epilogue 0");
+    TORCH_CHECK(c_in->device() == a.device() && c_in->scalar_type() == bf16 &&
+                c_in->dim() == 2 && c_in->size(0) == m && c_in->size(1) == n &&
+                c_in->stride(1) == 1, op,
+                ": c_in must be a bfloat16 [M, N] tensor with unit inner stride "
+                "on the device of a");
+    call.c = c_in.value();
+  } else {
+    auto opts = a.options().dtype(bf16);
+    call.c = batched ? torch::empty({batch, m, n}, opts) : torch::empty({m, n}, opts);
+  }
+  const bool reads_bias = fp8 ? bias.has_value() : (epilogue == 1 || epilogue == 2);
+  TORCH_CHECK(bias.has_value() == reads_bias, op, ": bias must be given exactly "
+              "when the epilogue reads it (epilogue 1 or 2)");
+  if (reads_bias) {
+    TORCH_CHECK(bias->device() == a.device(), op, ": bias must be on the device of a");
+    TORCH_CHECK(bias->scalar_type() == bf16 && bias->is_contiguous(), op,
+                ": bias must be contiguous bfloat16");
+    if (batched) {
+      TORCH_CHECK(bias->dim() == 2 && bias->size(0) == batch && bias->size(1) == n,
+                  op, ": bias must be [batch, N]");
+    } else {
+      TORCH_CHECK(bias->numel() == n, op, ": bias must have N elements");
+    }
+    g.bias = bias->const_data_ptr();
+    g.bias_bs = batched ? n : 0;
+  }
+  TORCH_CHECK(aux_in.has_value() == (epilogue == 3), op,
+              ": aux_in must be given exactly for epilogue 3 (dgelu)");
+  if (epilogue == 3) {
+    // the kernel walks aux with c's row stride
+    TORCH_CHECK(aux_in->device() == a.device() && aux_in->scalar_type() == bf16 &&
+                aux_in->dim() == 2 && aux_in->size(0) == m && aux_in->size(1) == n &&
+                aux_in->is_contiguous(), op,
+                ": aux_in must be a contiguous bfloat16 [M, N] tensor on the device of a");
+    g.aux = const_cast<void*>(aux_in->const_data_ptr());
+  } else if (epilogue == 2) {
+    call.aux = torch::empty({m, n}, a.options());
+    g.aux = call.aux.mutable_data_ptr();
+  }
+  g.a = a.const_data_ptr();
+  g.b = b.const_data_ptr();
+  g.c = call.c.mutable_data_ptr();
+  g.m = m; g.n = n; g.k = k;
+  g.lda = a.stride(-2); g.ldb = b.stride(-2); g.ldc = call.c.stride(-2);
+  g.batch = batch;
+  if (batched) {
+    g.a_bs = a.stride(0); g.b_bs = b.stride(0); g.c_bs = call.c.stride(0);
+  }
+  g.layout = (int)layout;
+  g.epilogue = (int)epilogue;
+  g.accumulate = accumulate;
+  g.scale_ab = (float)scale_ab;
+  return call;
+}
+
+// Returns {C}, or {C, aux} for bias_gelu.
 std::vector<Tensor> gemm_bf16_ex(const Tensor& a, const Tensor& b,
                                  int64_t layout, int64_t epilogue,
                                  const c10::optional<Tensor>& bias,
                                  const c10::optional<Tensor>& aux_in,
                                  const c10::optional<Tensor>& c_in) {
-  TORCH_CHECK(a.is_cuda() && a.scalar_type() == torch::kBFloat16);
-  TORCH_CHECK(b.is_cuda() && b.scalar_type() == torch::kBFloat16);
-  TORCH_CHECK(a.dim() == 2 && b.dim() == 2);
-  TORCH_CHECK(a.stride(1) == 1 && b.stride(1) == 1, "row-major inputs only");
-  int64_t m, n, k;
-  if (layout == 0) {        // A[m][k] x Bt[n][k]
-    m = a.size(0); k = a.size(1); n = b.size(0);
-    TORCH_CHECK(b.size(1) == k, "gemm NT: inner dims mismatch");
-  } else if (layout == 1) { // A[m][k] x B[k][n]
-    m = a.size(0); k = a.size(1); n = b.size(1);
-    TORCH_CHECK(b.size(0) == k, "gemm NN: inner dims mismatch");
-  } else {                  // At[k][m] x B[k][n]
-    k = a.size(0); m = a.size(1); n = b.size(1);
-    TORCH_CHECK(b.size(0) == k, "gemm TN: inner dims mismatch");
-  }
-  TORCH_CHECK(k >= 64, "gemm_bf16_ex: K must be >= 64");
-  bool accumulate = c_in.has_value();
-  Tensor c;
-  if (accumulate) {
-    c = c_in.value();
-    TORCH_CHECK(c.size(0) == m && c.size(1) == n && c.stride(1) == 1 &&
-                c.scalar_type() == torch::kBFloat16);
-    TORCH_CHECK(epilogue == 0, "accumulate requires epilogue=none");
-  } else {
-    c = torch::empty({m, n}, a.options());
-  }
-  const void* bias_p = nullptr;
-  if (epilogue == 1 || epilogue == 2) {
-    TORCH_CHECK(bias.has_value() && bias->numel() == n &&
-                bias->scalar_type() == torch::kBFloat16 && bias->is_contiguous());
-    bias_p = bias->const_data_ptr();
-  }
-  Tensor aux;
-  void* aux_p = nullptr;
-  if (epilogue == 2) {
-    aux = torch::empty({m, n}, a.options());
-    aux_p = aux.mutable_data_ptr();
-  } else if (epilogue == 3) {
-    TORCH_CHECK(aux_in.has_value() && aux_in->size(0) == m &&
-                aux_in->size(1) == n && aux_in->stride(1) == 1 &&
-                aux_in->scalar_type() == torch::kBFloat16);
-    aux_p = const_cast<void*>(aux_in->const_data_ptr());
-  }
-  pa::gemm_bf16_ex(a.const_data_ptr(), b.const_data_ptr(), c.mutable_data_ptr(),
-                   bias_p, aux_p, m, n, k, a.stride(0), b.stride(0), c.stride(0),
-                   (int)layout, (int)epilogue, accumulate, cur_stream());
-  if (epilogue == 2) return {c, aux};
-  return {c};
+  auto call = check_gemm("gemm_bf16_ex", false, false, a, b, "b", layout,
+                         epilogue, bias, aux_in, c_in, 1.0);
+  pa::gemm_bf16(call.g, cur_stream());
+  if (epilogue == 2) return {call.c, call.aux};
+  return {call.c};
+}
+
+// Batched NT (grouped experts): C[z] = A[z] @ Bt[z]^T.  The MoE backward is
+// the client: dg = dy @ w2^T and dx = dz @ w1^T hit the stored [E, rows, K]
+// weight layout directly, dodging both the hipBLASLt strided-transB fault
+// (see models/moe.py) and the contiguous weight-transpose workaround.
+Tensor gemm_bf16_nt_batched(const Tensor& a, const Tensor& bt) {
+  auto call = check_gemm("gemm_bf16_nt_batched", false, true, a, bt, "bt", 0, 0,
+                         c10::nullopt, c10::nullopt, c10::nullopt, 1.0);
+  pa::gemm_bf16(call.g, cur_stream());
+  return call.c;
 }
 
 Tensor gemm_fp8_nt(const Tensor& a, const Tensor& bt, double scale_ab,
                    const c10::optional<Tensor>& bias) {
-  TORCH_CHECK(a.is_cuda() && a.dim() == 2 && bt.dim() == 2);
-  TORCH_CHECK(a.scalar_type() == torch::kFloat8_e4m3fn ||
-              a.scalar_type() == torch::kUInt8, "gemm_fp8: e4m3/uint8 input");
-  TORCH_CHECK(a.stride(1) == 1 && bt.stride(1) == 1, "row-major inputs");
-  int64_t m = a.size(0), k = a.size(1), n = bt.size(0);
-  TORCH_CHECK(bt.size(1) == k && k >= 128);
-  auto c = torch::empty({m, n}, a.options().dtype(torch::kBFloat16));
-  const void* bp = nullptr;
-  if (bias.has_value()) {
-    TORCH_CHECK(bias->scalar_type() == torch::kBFloat16 && bias->numel() == n);
-    bp = bias->const_data_ptr();
-  }
-  pa::gemm_fp8_nt(a.const_data_ptr(), bt.const_data_ptr(), c.mutable_data_ptr(),
-                  bp, (float)scale_ab, m, n, k, a.stride(0), bt.stride(0),
-                  c.stride(0), cur_stream());
-  return c;
+  auto call = check_gemm("gemm_fp8_nt", true, false, a, bt, "bt", 0, 0, bias,
+                         c10::nullopt, c10::nullopt, scale_ab);
+  pa::gemm_fp8(call.g, cur_stream());
+  return call.c;
 }
 
-Tensor decode_gemm(const Tensor& x, const Tensor& w,
-                   const c10::optional<Tensor>& bias) {
-  CHECK_IN(x);
-  TORCH_CHECK(x.dim() == 2 && w.dim() == 2 && w.stride(1) == 1);
-  TORCH_CHECK(x.scalar_type() == torch::kBFloat16);
-  int64_t m = x.size(0), k = x.size(1), n = w.size(1);
-  TORCH_CHECK(w.size(0) == k && m <= 32);
-  int64_t ntiles = (n + 1023) / 1024;
-  int64_t ksplit = std::min<int64_t>(std::max<int64_t>(1, 768 / std::max<int64_t>(ntiles, 1)),
-                                     std::max<int64_t>(1, k / 128));
-  int64_t mt = m <= 8 ? 8 : (m <= 16 ? 16 : 32);
-  auto ws = torch::empty({ksplit, mt, n}, x.options().dtype(torch::kFloat));
-  auto y = torch::empty({m, n}, x.options());
-  pa::decode_gemm(x.const_data_ptr(), w.const_data_ptr(),
-                  bias.has_value() ? bias->const_data_ptr() : nullptr,
-                  y.mutable_data_ptr(), ws.mutable_data_ptr<float>(), m, n, k,
-                  w.stride(0), ksplit, cur_stream());
-  return y;
+// grouped/batched variant: one launch over all experts, bias [E, N]
+Tensor gemm_fp8_nt_batched(const Tensor& a, const Tensor& bt, double scale_ab,
+                           const c10::optional<Tensor>& bias) {
+  auto call = check_gemm("gemm_fp8_nt_batched", true, true, a, bt, "bt", 0, 0,
+                         bias, c10::nullopt, c10::nullopt, scale_ab);
+  pa::gemm_fp8(call.g, cur_stream());
+  return call.c;
 }
 
 // Contract of the MFMA W-streamer (decode_stream_kernel, docs/KERNELS.md),
@@ -1208,10 +1249,6 @@ struct DecodeStreamCall {
   const void* bias;
   Tensor ws, y;
 };
-
-static bool aligned16(const Tensor& t) {
-  return reinterpret_cast<uintptr_t>(t.const_data_ptr()) % 16 == 0;
-}
 
 static DecodeStreamCall check_decode_stream(const char* op, const Tensor& x,
                                             const Tensor& w, int64_t k,
@@ -1362,59 +1399,12 @@ std::vector<Tensor> moe_assign_slots(const Tensor& topi, int64_t num_experts,
   return {slot, counts};
 }
 
-Tensor gemm_fp8_nt_batched(const Tensor& a, const Tensor& bt, double scale_ab,
-                           const c10::optional<Tensor>& bias) {
-  TORCH_CHECK(a.is_cuda() && a.dim() == 3 && bt.dim() == 3);
-  TORCH_CHECK(a.is_contiguous() && bt.is_contiguous());
-  int64_t e = a.size(0), m = a.size(1), k = a.size(2), n = bt.size(1);
-  TORCH_CHECK(bt.size(0) == e && bt.size(2) == k && k >= 128);
-  const void* bp = nullptr;
-  int64_t bias_bs = 0;
-  if (bias.has_value()) {
-    TORCH_CHECK(bias->is_contiguous() && bias->scalar_type() == torch::kBFloat16);
-    TORCH_CHECK(bias->dim() == 2 && bias->size(0) == e && bias->size(1) == n);
-    bp = bias->const_data_ptr();
-    bias_bs = n;
-  }
-  auto c = torch::empty({e, m, n}, a.options().dtype(torch::kBFloat16));
-  pa::gemm_fp8_nt_batched(a.const_data_ptr(), bt.const_data_ptr(),
-                          c.mutable_data_ptr(), bp, (float)scale_ab, e,
-                          m, n, k, k, k, n, m * k, n * k, m * n, cur_stream(),
-                          bias_bs);
-  return c;
-}
-
 Tensor amax_abs(const Tensor& x) {
   CHECK_IN(x);
   auto out = torch::zeros({}, x.options().dtype(torch::kFloat));
   pa::amax_abs(x.const_data_ptr(), out.mutable_data_ptr<float>(), x.numel(),
                dt_of(x), cur_stream());
   return out;
-}
-
-Tensor gemm_bf16_8p_t(const Tensor& a, const Tensor& bt) {
-  TORCH_CHECK(a.is_cuda() && a.dim() == 2 && bt.dim() == 2);
-  TORCH_CHECK(a.is_contiguous() && bt.is_contiguous());
-  int64_t m = a.size(0), k = a.size(1), n = bt.size(0);
-  TORCH_CHECK(bt.size(1) == k && m % 256 == 0 && n % 256 == 0 && k % 32 == 0);
-  auto c = torch::empty({m, n}, a.options());
-  pa::gemm_bf16_8p(a.const_data_ptr(), bt.const_data_ptr(),
-                   c.mutable_data_ptr(), m, n, k, k, k, n, cur_stream());
-  return c;
-}
-
-Tensor gemm_bf16_nt_batched_t(const Tensor& a, const Tensor& bt) {
-  TORCH_CHECK(a.is_cuda() && a.dim() == 3 && bt.dim() == 3);
-  TORCH_CHECK(a.scalar_type() == torch::kBFloat16 &&
-              bt.scalar_type() == torch::kBFloat16);
-  TORCH_CHECK(a.is_contiguous() && bt.is_contiguous());
-  int64_t e = a.size(0), m = a.size(1), k = a.size(2), n = bt.size(1);
-  TORCH_CHECK(bt.size(0) == e && bt.size(2) == k && k % 8 == 0 && n % 8 == 0);
-  auto c = torch::empty({e, m, n}, a.options());
-  pa::gemm_bf16_nt_batched(a.const_data_ptr(), bt.const_data_ptr(),
-                           c.mutable_data_ptr(), e, m, n, k, k, k, n,
-                           m * k, n * k, m * n, cur_stream());
-  return c;
 }
 
 Tensor quant_fp8(const Tensor& x, double scale) {
@@ -1484,7 +1474,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("fc1_gelu_fwd", &pa_lt::fc1_gelu_fwd);
   m.def("fc2_dgrad_dgelu", &pa_lt::fc2_dgrad_dgelu);
   m.def("lt_epilogue_probe", &pa_lt::lt_epilogue_probe);
-  m.def("weight_only_gemv", &weight_only_gemv);
   m.def("l2norm_sq", &l2norm_sq);
   m.def("flash_attn_fwd", &flash_attn_fwd, py::arg("q"), py::arg("k"),
         py::arg("v"), py::arg("o") = c10::nullopt, py::arg("scale"),
@@ -1492,8 +1481,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("pdrop") = 0.0, py::arg("seed") = 0, py::arg("offset") = 0);
   m.def("fa_dropout_mask", &fa_dropout_mask);
   m.def("mfma_probe_fp8mx", &mfma_probe_fp8mx);
-  m.def("decode_gemm", &decode_gemm, py::arg("x"), py::arg("w"),
-        py::arg("bias") = c10::nullopt);
   m.def("decode_gemm_mfma", &decode_gemm_mfma, py::arg("x"), py::arg("w"),
         py::arg("bias") = c10::nullopt);
   m.def("decode_gemm_int8", &decode_gemm_int8, py::arg("x"), py::arg("qw"),
@@ -1531,9 +1518,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("dropout_add_bwd", &dropout_add_bwd);
   m.def("embedding_fwd", &embedding_fwd);
   m.def("embedding_bwd", &embedding_bwd);
-  m.def("gemm_bf16", &gemm_bf16);
-  m.def("gemm_bf16_nt_batched", &gemm_bf16_nt_batched_t);
-  m.def("gemm_bf16_8p", &gemm_bf16_8p_t);
+  m.def("gemm_bf16_nt_batched", &gemm_bf16_nt_batched);
   m.def("gemm_bf16_ex", &gemm_bf16_ex, py::arg("a"), py::arg("b"),
         py::arg("layout"), py::arg("epilogue") = 0,
         py::arg("bias") = c10::nullopt, py::arg("aux") = c10::nullopt,

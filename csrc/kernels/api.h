@@ -248,56 +248,48 @@ struct PrefillAttnArgs {
 };
 void paged_prefill_attention(const PrefillAttnArgs& a, hipStream_t s);
 
-// ---- hand-written bf16 MFMA GEMM (C[m][n] = op(A) x op(B)) ----------------
-// b_is_nt: B passed as Bt[n][k] row-major (fast path); else B[k][n].
-void gemm_bf16_8p(const void* a, const void* b, void* c, int64_t m, int64_t n,
-                  int64_t k, int64_t lda, int64_t ldb, int64_t ldc,
-                  hipStream_t s);
-void gemm_bf16_nt_batched(const void* a, const void* b, void* c,
-                          int64_t batch, int64_t m, int64_t n, int64_t k,
-                          int64_t lda, int64_t ldb, int64_t ldc,
-                          int64_t a_bs, int64_t b_bs, int64_t c_bs,
-                          hipStream_t s);
-void gemm_bf16(const void* a, const void* b, void* c, int64_t m, int64_t n,
-               int64_t k, int64_t lda, int64_t ldb, int64_t ldc, bool b_is_nt,
-               hipStream_t s);
-
-// full variant with operand layout + fused epilogue:
-//   layout: 0=NT (A[m][k], Bt[n][k])  1=NN (A[m][k], B[k][n])
-//           2=TN (At[k][m], B[k][n])  -- wgrad
-//   epilogue: 0=none 1=+bias[n] 2=gelu(x+bias) writing pre-act to aux
-//             3=dgelu (out = C * gelu'(aux))
-//   accumulate: C += result (epilogue forced to none)
-void gemm_bf16_ex(const void* a, const void* b, void* c, const void* bias,
-                  void* aux, int64_t m, int64_t n, int64_t k, int64_t lda,
-                  int64_t ldb, int64_t ldc, int layout, int epilogue,
-                  bool accumulate, hipStream_t s);
-
-// weight-only int8 GEMV (decode): qweight [N,K] int8 rows, scale [N] fp32
-void weight_only_gemv(const void* x, const void* wq, const float* scale,
-                      const void* bias, void* out, int64_t m, int64_t n,
-                      int64_t k, int dtype, hipStream_t s);
-
-// fp8 e4m3 MX GEMM: C[m,n] (bf16) = scale_ab * (A_fp8[m,k] x Bt_fp8[n,k]^T)
-void gemm_fp8_nt(const void* a, const void* bt, void* c, const void* bias,
-                 float scale_ab, int64_t m, int64_t n, int64_t k, int64_t lda,
-                 int64_t ldb, int64_t ldc, hipStream_t s);
-// grouped/batched variant (one launch over all experts; *_bs = batch strides)
-void gemm_fp8_nt_batched(const void* a, const void* bt, void* c,
-                         const void* bias, float scale_ab, int64_t batch,
-                         int64_t m, int64_t n, int64_t k, int64_t lda,
-                         int64_t ldb, int64_t ldc, int64_t a_bs, int64_t b_bs,
-                         int64_t c_bs, hipStream_t s,
-                         int64_t bias_bs = 0);
+// ---- dense MFMA GEMM (gemm.hip bf16, gemm_fp8.hip e4m3) --------------------
+// C[z] = op(A[z]) x op(B[z]) for z = 0 .. batch-1, fp32 accumulate, bf16 C.
+//   layout  kGemmNT: A[m][k], Bt[n][k]   kGemmNN: A[m][k], B[k][n]
+//           kGemmTN: At[k][m], B[k][n] (wgrad).  fp8 is NT only.
+//   bf16 epilogue: none | + bias[n] | gelu(x + bias), pre-activation written
+//     to aux | x * gelu'(aux).  accumulate: C += result, epilogue none.
+//   fp8: C = scale_ab * (A x Bt^T) (+ bias[n] when bias != null); operands
+//     are OCP e4m3 bytes; epilogue / accumulate / aux are not read.
+// Contract (checked by the binding before any launch, docs/KERNELS.md):
+//   * a, b, bias, aux, c on one GPU; bias, aux, c bf16.
+//   * all rows have unit inner stride; lda / ldb / ldc are row strides and
+//     *_bs batch strides, in elements.
+//   * a and b are staged by 16-byte accesses (DMA and guarded vector loads)
+//     through lda / ldb / a_bs / b_bs: each is a multiple of 16 bytes (8 bf16,
+//     16 fp8) and the a / b base pointers are 16-byte aligned.  c, aux and
+//     bias are accessed element by element and need neither.
+//   * k >= 64 (bf16) or 128 (fp8); 1 <= m, n, k < 2^31; 1 <= batch <= 65535.
+//   * bias non-null exactly when the epilogue reads it: n elements, advanced
+//     by bias_bs per batch (fp8; the bf16 kernel shares one bias).
+//   * aux [m][n] with row stride ldc for the two GELU epilogues.
+enum GemmLayout : int { kGemmNT = 0, kGemmNN = 1, kGemmTN = 2 };
+enum GemmEpilogue : int {
+  kGemmEpiNone = 0, kGemmEpiBias = 1, kGemmEpiBiasGelu = 2, kGemmEpiDGelu = 3
+};
+struct GemmArgs {
+  const void *a, *b;
+  void* c;
+  const void* bias;
+  void* aux;
+  int64_t m, n, k;
+  int64_t lda, ldb, ldc;
+  int64_t batch;                       // grid.z; 1 = plain GEMM
+  int64_t a_bs, b_bs, c_bs, bias_bs;
+  int layout, epilogue;
+  bool accumulate;
+  float scale_ab;                      // fp8 only
+};
+void gemm_bf16(const GemmArgs& g, hipStream_t s);
+void gemm_fp8(const GemmArgs& g, hipStream_t s);
 // bf16 -> e4m3 cast with uniform scale (fused, no fp32 round-trip)
 void quant_fp8(const void* x, void* out, float scale, int64_t numel,
                hipStream_t s);
-
-// skinny decode GEMM (M<=32): y = x @ W[K,N] + bias, split-K partials
-// in `workspace` ([ksplit, padded_m, N] fp32)
-void decode_gemm(const void* x, const void* w, const void* bias, void* y,
-                 float* workspace, int64_t m, int64_t n, int64_t k,
-                 int64_t ldw, int64_t ksplit, hipStream_t s);
 
 // MFMA W-streaming decode GEMMs (decode_gemm.hip) for three weight formats.  1 <= M <= 32, N % 256 == 0, K % 64 == 0, K <= 2^24;
 // x bf16 [M, K] contiguous; x and weight base pointers 16-byte aligned.

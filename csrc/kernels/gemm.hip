@@ -33,8 +33,7 @@
 //   NN: A[M][K] rm, B[K][N] rm       (dgrad dY.W; B reg-transposed)
 //   TN: At[K][M] rm, B[K][N] rm      (wgrad dY^T.X; both reg-transposed)
 // Epilogues: NONE / BIAS / BIAS_GELU(+aux out) / DGELU(aux in) / ACC.
-#include "common.h"
-#include "api.h"
+#include "gemm_common.h"
 
 namespace pa {
 
@@ -47,8 +46,9 @@ __device__ __forceinline__ unsigned g_swz(unsigned row, unsigned col) {
   return row * 64 + (col ^ ((row & 7u) << 3));
 }
 
-enum { LAY_NT = 0, LAY_NN = 1, LAY_TN = 2 };
-enum { EPI_NONE = 0, EPI_BIAS = 1, EPI_BIAS_GELU = 2, EPI_DGELU = 3 };
+enum { LAY_NT = kGemmNT, LAY_NN = kGemmNN, LAY_TN = kGemmTN };
+enum { EPI_NONE = kGemmEpiNone, EPI_BIAS = kGemmEpiBias,
+       EPI_BIAS_GELU = kGemmEpiBiasGelu, EPI_DGELU = kGemmEpiDGelu };
 
 __device__ __forceinline__ float epi_gelu(float x) {
   // exact-erf GeLU (paddle default approximate=False), same poly as
@@ -78,10 +78,10 @@ __device__ __forceinline__ float epi_gelu_grad(float x) {
 // ---------------------------------------------------------------------------
 // the kernel
 // ---------------------------------------------------------------------------
-// FAST=true: interior-only instantiation (grid covers full 256x256 tiles,
-// K%64==0; no guarded code compiled in -> no spills).  FAST=false: guarded
-// boundary kernel launched over the full grid, early-exiting blocks the
-// fast launch already covered (skip_interior).
+// FAST=true: interior-only instantiation, NT only (grid covers full 256x256
+// tiles, K%64==0; no guarded code compiled in -> no spills).  FAST=false:
+// guarded boundary kernel launched over the full grid, early-exiting blocks
+// the fast launch already covered (skip_interior).
 template <int LAYOUT, int EPI, bool ACC, bool FAST>
 __launch_bounds__(512, 2)
 __global__ void gemm_bf16_kernel(const short* __restrict__ ag, const short* __restrict__ bg,
@@ -101,32 +101,11 @@ __global__ void gemm_bf16_kernel(const short* __restrict__ ag, const short* __re
   __shared__ short a_lds[2][BM * BK];
   __shared__ short b_lds[2][BN * BK];
 
-  // T1: XCD-aware bijective workgroup swizzle (contiguous chunks per XCD)
-  const int nwg = gridDim.x * gridDim.y;
-  int orig = blockIdx.y * gridDim.x + blockIdx.x;
-  {
-    const int nx = 8;
-    int q = nwg / nx, rr = nwg % nx;
-    int xcd = orig % nx, pos = orig / nx;
-    orig = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + pos;
-  }
-  // FAST grid spans only the interior tile rectangle
-  const int mt = FAST ? (M / BM) : ((M + BM - 1) / BM);
-  const int nt = FAST ? (N / BN) : ((N + BN - 1) / BN);
-  // Tile-group rasterization: GM consecutive bm-rows walk bn fastest, so
-  // the ~32 blocks concurrently resident on one XCD touch few A/B panels
-  // and their K-tile streams coincide in L2 (vs column-major order, which
-  // re-reads the B panel from HBM for every bm).
-  constexpr int GM = 8;
-  int bm, bn;
-  {
-    int band = orig / (GM * nt);
-    int rem = orig - band * (GM * nt);
-    int gm_band = mt - band * GM < GM ? mt - band * GM : GM;
-    bm = band * GM + rem % gm_band;
-    bn = rem / gm_band;
-  }
-  const int row0 = bm * BM, col0 = bn * BN;
+  static_assert(!FAST || LAYOUT == LAY_NT, "the 4-phase pipeline is NT-only");
+  static_assert(BM == kGemmTile && BN == kGemmTile, "gemm_common.h tile");
+
+  int row0, col0;
+  gemm_tile_origin<FAST>(M, N, row0, col0);
   if (!FAST && skip_interior &&
       row0 + BM <= M && col0 + BN <= N && (K % 64) == 0)
     return;  // covered by the fast launch
@@ -173,107 +152,65 @@ __global__ void gemm_bf16_kernel(const short* __restrict__ ag, const short* __re
         16, 0, 0);
   };
   auto stage_a_dma = [&](int buf, int kt) {
-    const long long k0 = (long long)kt * BK;
 #pragma unroll
-    for (int it = 0; it < 4; ++it) {
-      const short* src = ag + (long long)(row0 + s_r[it]) * lda + k0 + s_cp[it];
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) unsigned int*)src,
-          (__attribute__((address_space(3))) unsigned int*)&a_lds[buf][it * 4096 + tid * 8],
-          16, 0, 0);
-    }
+    for (int it = 0; it < 4; ++it) stage_a_round(buf, kt, it);
   };
   // B operand, DMA path (Bt[N][K] row-major; NT)
   auto stage_b_dma = [&](int buf, int kt) {
-    const long long k0 = (long long)kt * BK;
 #pragma unroll
-    for (int it = 0; it < 4; ++it) {
-      const short* src = bg + (long long)(col0 + s_r[it]) * ldb + k0 + s_cp[it];
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) unsigned int*)src,
-          (__attribute__((address_space(3))) unsigned int*)&b_lds[buf][it * 4096 + tid * 8],
-          16, 0, 0);
-    }
+    for (int it = 0; it < 4; ++it) stage_b_round(buf, kt, it);
   };
   const int rot = tid & 7;  // staggers transposed LDS writes across banks
 
   // ---- guarded (boundary / K-tail) staging: zero-fill out of range --------
-  auto stage_guarded = [&](int buf, int kt) {
-    const long long k0 = (long long)kt * BK;
-    // A
+  // Row-major operand src[limit][K] (A of NT/NN, Bt of NT): tile rows
+  // base.. land as LDS rows.
+  auto stage_rows = [&](const short* src, long long ld, int limit, int base,
+                        short* lds, long long k0) {
 #pragma unroll
     for (int it = 0; it < 4; ++it) {
       int flat = it * 4096 + tid * 8;
       int r = flat / BK, c = flat % BK;
       shortx8 v;
-      if (A_DMA) {
-        if (row0 + r < M && k0 + c + 7 < K)
-          v = *reinterpret_cast<const shortx8*>(ag + (long long)(row0 + r) * lda + k0 + c);
-        else
+      if (base + r < limit && k0 + c + 7 < K)
+        v = *reinterpret_cast<const shortx8*>(src + (long long)(base + r) * ld + k0 + c);
+      else
 #pragma unroll
-          for (int j = 0; j < 8; ++j)
-            v[j] = (row0 + r < M && k0 + c + j < K)
-                       ? ag[(long long)(row0 + r) * lda + k0 + c + j] : (short)0;
-        *reinterpret_cast<shortx8*>(&a_lds[buf][g_swz(r, c)]) = v;
+        for (int j = 0; j < 8; ++j)
+          v[j] = (base + r < limit && k0 + c + j < K)
+                     ? src[(long long)(base + r) * ld + k0 + c + j] : (short)0;
+      *reinterpret_cast<shortx8*>(&lds[g_swz(r, c)]) = v;
+    }
+  };
+  // K-major operand src[K][limit] (At of TN, B of NN/TN): read k-rows,
+  // scatter-transpose into lds[m|n][k].
+  auto stage_transposed = [&](const short* src, long long ld, int limit,
+                              int base, short* lds, long long k0) {
+#pragma unroll
+    for (int it = 0; it < 4; ++it) {
+      int flat = it * 4096 + tid * 8;
+      int kr = flat / BN, nc = flat % BN;
+      shortx8 v;
+      if (k0 + kr < K && base + nc + 7 < limit)
+        v = *reinterpret_cast<const shortx8*>(src + (k0 + kr) * ld + base + nc);
+      else
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+          v[j] = (k0 + kr < K && base + nc + j < limit)
+                     ? src[(k0 + kr) * ld + base + nc + j] : (short)0;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        int i = (j + rot) & 7;
+        lds[g_swz(nc + i, kr)] = v[i];
       }
     }
-    if (!A_DMA) {
-      // At[K][M]: read k-rows, scatter-transpose into a_lds[m][k]
-#pragma unroll
-      for (int it = 0; it < 4; ++it) {
-        int flat = it * 4096 + tid * 8;
-        int kr = flat / BN, nc = flat % BN;
-        shortx8 v;
-        if (k0 + kr < K && row0 + nc + 7 < M)
-          v = *reinterpret_cast<const shortx8*>(ag + (k0 + kr) * lda + row0 + nc);
-        else
-#pragma unroll
-          for (int j = 0; j < 8; ++j)
-            v[j] = (k0 + kr < K && row0 + nc + j < M)
-                       ? ag[(k0 + kr) * lda + row0 + nc + j] : (short)0;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          int i = (j + rot) & 7;
-          a_lds[buf][g_swz(nc + i, kr)] = v[i];
-        }
-      }
-    }
-    // B
-    if (B_DMA) {
-#pragma unroll
-      for (int it = 0; it < 4; ++it) {
-        int flat = it * 4096 + tid * 8;
-        int r = flat / BK, c = flat % BK;
-        shortx8 v;
-        if (col0 + r < N && k0 + c + 7 < K)
-          v = *reinterpret_cast<const shortx8*>(bg + (long long)(col0 + r) * ldb + k0 + c);
-        else
-#pragma unroll
-          for (int j = 0; j < 8; ++j)
-            v[j] = (col0 + r < N && k0 + c + j < K)
-                       ? bg[(long long)(col0 + r) * ldb + k0 + c + j] : (short)0;
-        *reinterpret_cast<shortx8*>(&b_lds[buf][g_swz(r, c)]) = v;
-      }
-    } else {
-#pragma unroll
-      for (int it = 0; it < 4; ++it) {
-        int flat = it * 4096 + tid * 8;
-        int kr = flat / BN, nc = flat % BN;
-        shortx8 v;
-        if (k0 + kr < K && col0 + nc + 7 < N)
-          v = *reinterpret_cast<const shortx8*>(bg + (k0 + kr) * ldb + col0 + nc);
-        else
-#pragma unroll
-          for (int j = 0; j < 8; ++j)
-            v[j] = (k0 + kr < K && col0 + nc + j < N)
-                       ? bg[(k0 + kr) * ldb + col0 + nc + j] : (short)0;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          int i = (j + rot) & 7;
-          b_lds[buf][g_swz(nc + i, kr)] = v[i];
-        }
-      }
-    }
+  };
+  auto stage_guarded = [&](int buf, int kt) {
+    const long long k0 = (long long)kt * BK;
+    if (A_DMA) stage_rows(ag, lda, M, row0, a_lds[buf], k0);
+    else       stage_transposed(ag, lda, M, row0, a_lds[buf], k0);
+    if (B_DMA) stage_rows(bg, ldb, N, col0, b_lds[buf], k0);
+    else       stage_transposed(bg, ldb, N, col0, b_lds[buf], k0);
   };
 
   floatx4 acc[8][4];
@@ -317,7 +254,7 @@ __global__ void gemm_bf16_kernel(const short* __restrict__ ag, const short* __re
     GEMM_SETPRIO(0);
   };
 
-  if constexpr (FAST && LAYOUT == LAY_NT) {
+  if constexpr (FAST) {
     // =======================================================================
     // fast path (NT only): 4-phase counted-vmcnt pipeline (T3+T4), T5.
     //
@@ -447,86 +384,49 @@ __global__ void gemm_bf16_kernel(const short* __restrict__ ag, const short* __re
 }
 
 // ---------------------------------------------------------------------------
-// host launcher
+// host launcher: GemmArgs (api.h) -> one kernel pair of the table
 // ---------------------------------------------------------------------------
-void gemm_bf16_ex(const void* a, const void* b, void* c, const void* bias,
-                  void* aux, int64_t m, int64_t n, int64_t k, int64_t lda,
-                  int64_t ldb, int64_t ldc, int layout, int epilogue,
-                  bool accumulate, hipStream_t s) {
-  const int mi = (int)(m / 256), ni = (int)(n / 256);      // interior tiles
-  const int gm = (int)((m + 255) / 256), gn = (int)((n + 255) / 256);
-  const bool k_ok = (k % 64 == 0);
-  // the 8-phase pipeline is NT-only; NN/TN run the guarded kernel (the
-  // autotune table keeps them off the hot path where hipBLASLt wins)
-  const bool has_fast = k_ok && mi > 0 && ni > 0 && layout == LAY_NT;
-  const bool has_edge = !has_fast || mi < gm || ni < gn;
-  dim3 blk(512);
-#define LAUNCH(L, E, AC)                                                       \
-  do {                                                                         \
-    if (has_fast)                                                              \
-      hipLaunchKernelGGL((gemm_bf16_kernel<L, E, AC, true>),                   \
-                         dim3((unsigned)mi, (unsigned)ni), blk, 0, s,          \
-                         (const short*)a, (const short*)b, (short*)c,          \
-                         (const short*)bias, (short*)aux, (int)m, (int)n,      \
-                         (int)k, lda, ldb, ldc, 0);                            \
-    if (has_edge)                                                              \
-      hipLaunchKernelGGL((gemm_bf16_kernel<L, E, AC, false>),                  \
-                         dim3((unsigned)gm, (unsigned)gn), blk, 0, s,          \
-                         (const short*)a, (const short*)b, (short*)c,          \
-                         (const short*)bias, (short*)aux, (int)m, (int)n,      \
-                         (int)k, lda, ldb, ldc, has_fast ? 1 : 0);             \
-  } while (0)
-#define EPI_SWITCH(L)                                                        \
-  do {                                                                       \
-    if (accumulate) { LAUNCH(L, EPI_NONE, true); }                           \
-    else if (epilogue == EPI_BIAS) { LAUNCH(L, EPI_BIAS, false); }           \
-    else if (epilogue == EPI_BIAS_GELU) { LAUNCH(L, EPI_BIAS_GELU, false); } \
-    else if (epilogue == EPI_DGELU) { LAUNCH(L, EPI_DGELU, false); }         \
-    else { LAUNCH(L, EPI_NONE, false); }                                     \
-  } while (0)
-  if (layout == LAY_NT) EPI_SWITCH(LAY_NT);
-  else if (layout == LAY_NN) EPI_SWITCH(LAY_NN);
-  else EPI_SWITCH(LAY_TN);
-#undef EPI_SWITCH
-#undef LAUNCH
-}
+using GemmBf16Kernel = void (*)(const short*, const short*, short*, const short*,
+                                short*, int, int, int, long long, long long,
+                                long long, int, long long, long long, long long);
+template <int L, int E, bool ACC, bool FAST>
+constexpr GemmBf16Kernel kern = gemm_bf16_kernel<L, E, ACC, FAST>;
 
-// Batched NT (grouped experts): C[z] = A[z] @ B[z]^T, z = 0..batch-1.
-// The MoE backward is the client: dg = dy @ w2^T and dx = dz @ w1^T hit
-// the stored [E, rows, K] weight layout directly, dodging both the
-// hipBLASLt strided-transB fault (see models/moe.py) and the contiguous
-// weight-transpose workaround.
-void gemm_bf16_nt_batched(const void* a, const void* b, void* c,
-                          int64_t batch, int64_t m, int64_t n, int64_t k,
-                          int64_t lda, int64_t ldb, int64_t ldc,
-                          int64_t a_bs, int64_t b_bs, int64_t c_bs,
-                          hipStream_t s) {
-  const int mi = (int)(m / 256), ni = (int)(n / 256);
-  const int gm = (int)((m + 255) / 256), gn = (int)((n + 255) / 256);
-  const bool k_ok = (k % 64 == 0);
-  const bool has_fast = k_ok && mi > 0 && ni > 0;
-  const bool has_edge = !has_fast || mi < gm || ni < gn;
-  dim3 blk(512);
-  if (has_fast)
-    hipLaunchKernelGGL((gemm_bf16_kernel<LAY_NT, EPI_NONE, false, true>),
-                       dim3((unsigned)mi, (unsigned)ni, (unsigned)batch), blk,
-                       0, s, (const short*)a, (const short*)b, (short*)c,
-                       nullptr, nullptr, (int)m, (int)n, (int)k, lda, ldb, ldc,
-                       0, a_bs, b_bs, c_bs);
-  if (has_edge)
-    hipLaunchKernelGGL((gemm_bf16_kernel<LAY_NT, EPI_NONE, false, false>),
-                       dim3((unsigned)gm, (unsigned)gn, (unsigned)batch), blk,
-                       0, s, (const short*)a, (const short*)b, (short*)c,
-                       nullptr, nullptr, (int)m, (int)n, (int)k, lda, ldb, ldc,
-                       has_fast ? 1 : 0, a_bs, b_bs, c_bs);
-}
+// The 20 launchable kernels, [layout][variant][fast]; variant is the epilogue,
+// or 4 for accumulate.  The 4-phase pipeline is NT-only: NN / TN run the
+// guarded kernel over the whole grid (the autotune table keeps them off the
+// hot path where hipBLASLt wins).
+static const GemmBf16Kernel kGemmBf16Kernels[3][5][2] = {
+    {{kern<LAY_NT, EPI_NONE, false, false>, kern<LAY_NT, EPI_NONE, false, true>},
+     {kern<LAY_NT, EPI_BIAS, false, false>, kern<LAY_NT, EPI_BIAS, false, true>},
+     {kern<LAY_NT, EPI_BIAS_GELU, false, false>, kern<LAY_NT, EPI_BIAS_GELU, false, true>},
+     {kern<LAY_NT, EPI_DGELU, false, false>, kern<LAY_NT, EPI_DGELU, false, true>},
+     {kern<LAY_NT, EPI_NONE, true, false>, kern<LAY_NT, EPI_NONE, true, true>}},
+    {{kern<LAY_NN, EPI_NONE, false, false>, nullptr},
+     {kern<LAY_NN, EPI_BIAS, false, false>, nullptr},
+     {kern<LAY_NN, EPI_BIAS_GELU, false, false>, nullptr},
+     {kern<LAY_NN, EPI_DGELU, false, false>, nullptr},
+     {kern<LAY_NN, EPI_NONE, true, false>, nullptr}},
+    {{kern<LAY_TN, EPI_NONE, false, false>, nullptr},
+     {kern<LAY_TN, EPI_BIAS, false, false>, nullptr},
+     {kern<LAY_TN, EPI_BIAS_GELU, false, false>, nullptr},
+     {kern<LAY_TN, EPI_DGELU, false, false>, nullptr},
+     {kern<LAY_TN, EPI_NONE, true, false>, nullptr}},
+};
 
-// legacy entry (round-1 API): b_is_nt picks NT vs NN, no epilogue
-void gemm_bf16(const void* a, const void* b, void* c, int64_t m, int64_t n,
-               int64_t k, int64_t lda, int64_t ldb, int64_t ldc, bool b_is_nt,
-               hipStream_t s) {
-  gemm_bf16_ex(a, b, c, nullptr, nullptr, m, n, k, lda, ldb, ldc,
-               b_is_nt ? LAY_NT : LAY_NN, EPI_NONE, false, s);
+void gemm_bf16(const GemmArgs& g, hipStream_t s) {
+  const auto& pair = kGemmBf16Kernels[g.layout][g.accumulate ? 4 : g.epilogue];
+  const GemmPlan plan = gemm_plan(g, 64, pair[1] != nullptr);
+  gemm_launch(plan, pair[1], pair[0],
+              [&](GemmBf16Kernel k, dim3 grid, int skip_interior) {
+    hipLaunchKernelGGL(k, grid, dim3(512), 0, s, (const short*)g.a,
+                       (const short*)g.b, (short*)g.c, (const short*)g.bias,
+                       (short*)g.aux, (int)g.m, (int)g.n, (int)g.k,
+                       (long long)g.lda, (long long)g.ldb, (long long)g.ldc,
+                       skip_interior, (long long)g.a_bs, (long long)g.b_bs,
+                       (long long)g.c_bs);
+  });
 }
 
 }  // namespace pa
+

@@ -12,8 +12,7 @@
 // Structure: the bf16 8-phase-derived 4-phase counted-vmcnt pipeline from
 // gemm.hip, reused byte-for-byte -- an fp8 [256][128] tile has the same
 // byte geometry as bf16 [256][64] (128 B rows, 16 B-granule XOR swizzle).
-#include "common.h"
-#include "api.h"
+#include "gemm_common.h"
 
 namespace pa {
 
@@ -50,26 +49,9 @@ __global__ void gemm_fp8_kernel(const unsigned char* __restrict__ ag,
   __shared__ unsigned char a_lds[2][BM * BK];
   __shared__ unsigned char b_lds[2][BN * BK];
 
-  const int nwg = gridDim.x * gridDim.y;
-  int orig = blockIdx.y * gridDim.x + blockIdx.x;
-  {
-    const int nx = 8;
-    int q = nwg / nx, rr = nwg % nx;
-    int xcd = orig % nx, pos = orig / nx;
-    orig = (xcd < rr ? xcd * (q + 1) : rr * (q + 1) + (xcd - rr) * q) + pos;
-  }
-  const int mt = FAST ? (M / BM) : ((M + BM - 1) / BM);
-  const int nt = FAST ? (N / BN) : ((N + BN - 1) / BN);
-  constexpr int GM = 8;
-  int bm, bn;
-  {
-    int band = orig / (GM * nt);
-    int rem = orig - band * (GM * nt);
-    int gm_band = mt - band * GM < GM ? mt - band * GM : GM;
-    bm = band * GM + rem % gm_band;
-    bn = rem / gm_band;
-  }
-  const int row0 = bm * BM, col0 = bn * BN;
+  static_assert(BM == kGemmTile && BN == kGemmTile, "gemm_common.h tile");
+  int row0, col0;
+  gemm_tile_origin<FAST>(M, N, row0, col0);
   if (!FAST && skip_interior &&
       row0 + BM <= M && col0 + BN <= N && (K % BK) == 0)
     return;
@@ -101,20 +83,19 @@ __global__ void gemm_fp8_kernel(const unsigned char* __restrict__ ag,
         (__attribute__((address_space(3))) unsigned int*)&a_lds[buf][it * 8192 + tid * 16],
         16, 0, 0);
   };
-  auto stage_a_dma = [&](int buf, int kt) {
+  auto stage_b_round = [&](int buf, int kt, int it) {
+    const long long k0 = (long long)kt * BK;
+    const unsigned char* src = bg + (long long)(col0 + s_r[it]) * ldb + k0 + s_cp[it];
+    __builtin_amdgcn_global_load_lds(
+        (const __attribute__((address_space(1))) unsigned int*)src,
+        (__attribute__((address_space(3))) unsigned int*)&b_lds[buf][it * 8192 + tid * 16],
+        16, 0, 0);
+  };
+  auto stage_dma = [&](int buf, int kt) {
 #pragma unroll
     for (int it = 0; it < 4; ++it) stage_a_round(buf, kt, it);
-  };
-  auto stage_b_dma = [&](int buf, int kt) {
-    const long long k0 = (long long)kt * BK;
 #pragma unroll
-    for (int it = 0; it < 4; ++it) {
-      const unsigned char* src = bg + (long long)(col0 + s_r[it]) * ldb + k0 + s_cp[it];
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) unsigned int*)src,
-          (__attribute__((address_space(3))) unsigned int*)&b_lds[buf][it * 8192 + tid * 16],
-          16, 0, 0);
-    }
+    for (int it = 0; it < 4; ++it) stage_b_round(buf, kt, it);
   };
   auto stage_guarded = [&](int buf, int kt) {
     const long long k0 = (long long)kt * BK;
@@ -182,51 +163,36 @@ __global__ void gemm_fp8_kernel(const unsigned char* __restrict__ ag,
     __builtin_amdgcn_s_setprio(0);
   };
 
-  if constexpr (FAST) {
-    // simple 2-barrier DMA pipeline (the bf16 kernel's deeper 4-phase
-    // schedule spilled here: fp8 fragments are 2x the registers)
-    stage_a_dma(0, 0);
-    stage_b_dma(0, 0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  // Simple 2-barrier pipeline for both kernels (the bf16 kernel's deeper
+  // 4-phase schedule spilled here: fp8 fragments are 2x the registers).  The
+  // fast kernel stages by DMA, which only vmcnt tracks; the guarded staging
+  // also writes LDS from registers.
+  auto stage = [&](int buf, int kt) {
+    if constexpr (FAST) stage_dma(buf, kt);
+    else stage_guarded(buf, kt);
+  };
+  auto wait_staged = [&]() {
+    if constexpr (FAST) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     __syncthreads();
-    for (int kt = 0; kt < nkt; ++kt) {
-      const int cur = kt & 1;
-      if (kt + 1 < nkt) { stage_a_dma(cur ^ 1, kt + 1); stage_b_dma(cur ^ 1, kt + 1); }
-      read_a_half(cur, 0, afA);
-      read_b_half(cur, 0, bfA);
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      mfma_quadrant(afA, bfA, 0, 0);
-      read_b_half(cur, 1, bfB);
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      mfma_quadrant(afA, bfB, 0, 1);
-      read_a_half(cur, 1, afB);
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      mfma_quadrant(afB, bfB, 1, 1);
-      mfma_quadrant(afB, bfA, 1, 0);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-    }
-  } else {
-    stage_guarded(0, 0);
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    __syncthreads();
-    for (int kt = 0; kt < nkt; ++kt) {
-      const int cur = kt & 1;
-      if (kt + 1 < nkt) stage_guarded(cur ^ 1, kt + 1);
-      read_a_half(cur, 0, afA);
-      read_b_half(cur, 0, bfA);
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      mfma_quadrant(afA, bfA, 0, 0);
-      read_b_half(cur, 1, bfB);
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      mfma_quadrant(afA, bfB, 0, 1);
-      read_a_half(cur, 1, afB);
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      mfma_quadrant(afB, bfB, 1, 1);
-      mfma_quadrant(afB, bfA, 1, 0);
-      asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-      __syncthreads();
-    }
+  };
+  stage(0, 0);
+  wait_staged();
+  for (int kt = 0; kt < nkt; ++kt) {
+    const int cur = kt & 1;
+    if (kt + 1 < nkt) stage(cur ^ 1, kt + 1);
+    read_a_half(cur, 0, afA);
+    read_b_half(cur, 0, bfA);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    mfma_quadrant(afA, bfA, 0, 0);
+    read_b_half(cur, 1, bfB);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    mfma_quadrant(afA, bfB, 0, 1);
+    read_a_half(cur, 1, afB);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    mfma_quadrant(afB, bfB, 1, 1);
+    mfma_quadrant(afB, bfA, 1, 0);
+    wait_staged();
   }
 
   // epilogue: per-tensor dequant scale + optional bias, bf16 store
@@ -256,38 +222,19 @@ __global__ void gemm_fp8_kernel(const unsigned char* __restrict__ ag,
   }
 }
 
-void gemm_fp8_nt_batched(const void* a, const void* bt, void* c,
-                         const void* bias, float scale_ab, int64_t batch,
-                         int64_t m, int64_t n, int64_t k, int64_t lda,
-                         int64_t ldb, int64_t ldc, int64_t a_bs, int64_t b_bs,
-                         int64_t c_bs, hipStream_t s, int64_t bias_bs) {
-  const int mi = (int)(m / 256), ni = (int)(n / 256);
-  const int gm = (int)((m + 255) / 256), gn = (int)((n + 255) / 256);
-  const bool k_ok = (k % 128 == 0);
-  const bool has_fast = k_ok && mi > 0 && ni > 0;
-  const bool has_edge = !has_fast || mi < gm || ni < gn;
-  dim3 blk(512);
-  if (has_fast)
-    hipLaunchKernelGGL((gemm_fp8_kernel<true>),
-                       dim3((unsigned)mi, (unsigned)ni, (unsigned)batch),
-                       blk, 0, s, (const unsigned char*)a, (const unsigned char*)bt,
-                       (short*)c, (const short*)bias, scale_ab, (int)m, (int)n,
-                       (int)k, lda, ldb, ldc, 0, bias != nullptr,
-                       a_bs, b_bs, c_bs, bias_bs);
-  if (has_edge)
-    hipLaunchKernelGGL((gemm_fp8_kernel<false>),
-                       dim3((unsigned)gm, (unsigned)gn, (unsigned)batch),
-                       blk, 0, s, (const unsigned char*)a, (const unsigned char*)bt,
-                       (short*)c, (const short*)bias, scale_ab, (int)m, (int)n,
-                       (int)k, lda, ldb, ldc, has_fast ? 1 : 0, bias != nullptr,
-                       a_bs, b_bs, c_bs, bias_bs);
-}
-
-void gemm_fp8_nt(const void* a, const void* bt, void* c, const void* bias,
-                 float scale_ab, int64_t m, int64_t n, int64_t k, int64_t lda,
-                 int64_t ldb, int64_t ldc, hipStream_t s) {
-  gemm_fp8_nt_batched(a, bt, c, bias, scale_ab, 1, m, n, k, lda, ldb, ldc,
-                      0, 0, 0, s, 0);
+void gemm_fp8(const GemmArgs& g, hipStream_t s) {
+  using Kernel = decltype(&gemm_fp8_kernel<true>);
+  gemm_launch(gemm_plan(g, 128, true), Kernel(gemm_fp8_kernel<true>),
+              Kernel(gemm_fp8_kernel<false>),
+              [&](Kernel k, dim3 grid, int skip_interior) {
+    hipLaunchKernelGGL(k, grid, dim3(512), 0, s, (const unsigned char*)g.a,
+                       (const unsigned char*)g.b, (short*)g.c,
+                       (const short*)g.bias, g.scale_ab, (int)g.m, (int)g.n,
+                       (int)g.k, (long long)g.lda, (long long)g.ldb,
+                       (long long)g.ldc, skip_interior, g.bias != nullptr,
+                       (long long)g.a_bs, (long long)g.b_bs, (long long)g.c_bs,
+                       (long long)g.bias_bs);
+  });
 }
 
 // bf16 -> e4m3 cast with a uniform scale, packed x8 (v_cvt_pk_fp8_f32);

@@ -31,14 +31,11 @@ def linear(x, weight, bias=None, name=None):
     # hipBLASLt via addmm (bias fused in its epilogue).
     if hot._own_linear_ok(x, weight):
         return hot.fused_linear_own(x, weight, bias)
-    # NOTE: the M<=32 split-K VALU weight streamer (decode_gemm_kernel in
-    # decode_gemm.hip) was measured SLOWER in-situ than hipBLASLt's skinny
-    # tiles (VALU-bound at M=32); it stays available via _C.decode_gemm but
-    # is not dispatched.  The MFMA streamer in the same file
-    # (decode_gemm_mfma) IS dispatched, but only on the tall-K decode shape
-    # where it beats hipBLASLt cold-HBM (fc2: 51.3 vs 71.8 us at M32 K16384
-    # N4096 -- tools/bench_decode_gemm.py); lt already streams the wide-N
-    # shapes at 3.4-5.9 TB/s.  Inputs outside the kernel's contract
+    # The M<=32 MFMA weight streamer (decode_gemm_mfma in decode_gemm.hip) is
+    # dispatched only on the tall-K decode shape where it beats hipBLASLt
+    # cold-HBM (fc2: 51.3 vs 71.8 us at M32 K16384 N4096 --
+    # tools/bench_decode_gemm.py); lt already streams the wide-N shapes at
+    # 3.4-5.9 TB/s.  Inputs outside the kernel's contract
     # (hot._decode_gemm_native_ok) go to hipBLASLt as well.
     if (not torch.is_grad_enabled() and x.dim() >= 2 and x.is_cuda
             and not hot._tracing()

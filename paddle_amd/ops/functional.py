@@ -1583,8 +1583,15 @@ def fused_ffn(x, w1, b1, w2, b2):
 from . import gemm_dispatch as _gd  # noqa: E402
 
 
+def _own_dgrad_ok(dy2, w):
+    # dx = dy2 @ w^T: paddle's W[in, out] is the NT B-operand as stored
+    return _gd.use_own("nt", dy2.shape[0], w.shape[0], w.shape[1]) \
+        and _gd.own_gemm_ok(dy2, w, "nt")
+
+
 def _wgrad(x2, dy2):
-    if _gd.use_own("tn", x2.shape[1], dy2.shape[1], x2.shape[0]):
+    if _gd.use_own("tn", x2.shape[1], dy2.shape[1], x2.shape[0]) \
+            and _gd.own_gemm_ok(x2, dy2, "tn"):
         return _gd.gemm_tn(x2, dy2)
     return torch.matmul(x2.t(), dy2)
 
@@ -1616,7 +1623,7 @@ class _FusedLinearOwn(torch.autograd.Function):
     def backward(ctx, dy):
         x2, w = ctx.saved_tensors
         dy2 = dy.reshape(-1, dy.shape[-1]).contiguous()
-        dx = _gd.gemm_nt(dy2, w) if _gd.use_own("nt", dy2.shape[0], w.shape[0], w.shape[1]) \
+        dx = _gd.gemm_nt(dy2, w) if _own_dgrad_ok(dy2, w) \
             else torch.matmul(dy2, w.t())
         dw = _wgrad(x2, dy2)
         db = _colsum(dy2, w.dtype) if ctx.has_bias else None
@@ -1650,7 +1657,7 @@ class _FusedFFNOwn(torch.autograd.Function):
         dz = _gd.gemm_nt(dy2, w2, epilogue=3, aux=z)
         dw2 = _wgrad(g, dy2)
         db2 = _colsum(dy2, w2.dtype) if ctx.has_b2 else None
-        dx = _gd.gemm_nt(dz, w1) if _gd.use_own("nt", dz.shape[0], w1.shape[0], w1.shape[1]) \
+        dx = _gd.gemm_nt(dz, w1) if _own_dgrad_ok(dz, w1) \
             else torch.matmul(dz, w1.t())
         dw1 = _wgrad(x2, dz)
         db1 = _colsum(dz, w1.dtype)
@@ -1658,11 +1665,13 @@ class _FusedFFNOwn(torch.autograd.Function):
 
 
 def _own_linear_ok(x, w, layout="nt"):
-    if not (x.is_cuda and x.dtype == torch.bfloat16 and w.dtype == torch.bfloat16
-            and _ext.use_native(x)):
+    if not (_gd._native_ok(x) and w.dtype == torch.bfloat16):
         return False
     m = x.numel() // x.shape[-1]
-    return _gd.use_own(layout, m, w.shape[1], w.shape[0])
+    # x @ w as stored is the NN operand pair: the forward runs it as NT on
+    # W^T, the dgrad reads w itself, so both must meet the operand contract
+    return _gd.use_own(layout, m, w.shape[1], w.shape[0]) \
+        and _gd.own_gemm_ok(x.reshape(-1, x.shape[-1]), w, "nn")
 
 
 def fused_linear_own(x, w, bias=None):

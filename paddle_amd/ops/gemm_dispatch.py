@@ -62,6 +62,26 @@ def use_own(layout: str, m: int, n: int, k: int) -> bool:
     return False
 
 
+def _operand_ok(t: torch.Tensor) -> bool:
+    # both operands are staged by 16-byte accesses through their row stride
+    return (t.dim() == 2 and t.dtype == torch.bfloat16 and t.stride(1) == 1
+            and t.stride(0) % 8 == 0 and t.storage_offset() % 8 == 0)
+
+
+def own_gemm_ok(a: torch.Tensor, b: torch.Tensor, layout: str) -> bool:
+    """True when (a, b) meet the own kernel's operand contract (GemmArgs in
+    csrc/kernels/api.h): 2-D bf16, unit inner stride, row strides and storage
+    offsets that are multiples of 16 bytes, agreeing inner dimensions, K >= 64.
+    Pure (strides, offsets, dtypes); says nothing about speed -- that is
+    use_own().  Callers take the library path when it is False, so the
+    binding's checks never turn a former fallback into an error."""
+    if layout not in ("nt", "nn", "tn") or not (_operand_ok(a) and _operand_ok(b)):
+        return False
+    k = a.shape[0] if layout == "tn" else a.shape[1]
+    kb = b.shape[1] if layout == "nt" else b.shape[0]
+    return k == kb and k >= 64 and a.numel() > 0 and b.numel() > 0
+
+
 def _native_ok(x: torch.Tensor) -> bool:
     return x.is_cuda and x.dtype == torch.bfloat16 and _ext.use_native(x)
 

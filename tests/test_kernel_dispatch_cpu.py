@@ -540,3 +540,58 @@ def test_comparator_rejects_nan_shape_and_dtype():
     assert not _passes(lambda: compare("nan", torch.tensor([1.0, float("nan"), 1, 1]), ref, atol=1.0))
     assert not _passes(lambda: compare("shape", torch.ones(2, 2), ref))
     assert not _passes(lambda: compare("dtype", torch.ones(4, dtype=BF16), ref, dtype=F32))
+
+
+# ---------------------------------------------------------------------------
+# own GEMM operand contract (gemm_dispatch.own_gemm_ok)
+# ---------------------------------------------------------------------------
+def test_own_gemm_ok_truth_table():
+    from paddle_amd.ops.gemm_dispatch import own_gemm_ok
+
+    def z(*shape, dtype=torch.bfloat16):
+        return torch.zeros(*shape, dtype=dtype)
+
+    m, n, k = 16, 24, 64
+    # contiguous operands, each layout
+    assert own_gemm_ok(z(m, k), z(n, k), "nt")
+    assert own_gemm_ok(z(m, k), z(k, n), "nn")
+    assert own_gemm_ok(z(k, m), z(k, n), "tn")
+    # a row-sliced view keeps 16-byte rows and base: fine
+    assert own_gemm_ok(z(m + 8, k)[8:], z(n, k), "nt")
+    assert own_gemm_ok(z(m, 2 * k)[:, k:], z(n, k), "nt")
+    # sliced with a storage offset that is not a multiple of 16 bytes
+    assert not own_gemm_ok(z(m, k + 8)[:, 1:k + 1], z(n, k), "nt")
+    assert not own_gemm_ok(z(m, k), z(n, k + 8)[:, 4:k + 4], "nt")
+    assert not own_gemm_ok(z(m * k + 1)[1:].view(m, k), z(n, k), "nt")
+    # row stride that is not a multiple of 16 bytes, inner stride != 1
+    assert not own_gemm_ok(z(m, k + 4)[:, :k], z(n, k), "nt")
+    assert not own_gemm_ok(z(m, k), z(k, n + 4)[:, :n], "nn")
+    assert not own_gemm_ok(z(k, m).t(), z(n, k), "nt")
+    # dtypes
+    assert not own_gemm_ok(z(m, k, dtype=torch.float32), z(n, k), "nt")
+    assert not own_gemm_ok(z(m, k), z(n, k, dtype=torch.float16), "nt")
+    # ranks
+    assert not own_gemm_ok(z(k), z(n, k), "nt")
+    assert not own_gemm_ok(z(m, k), z(2, n, k), "nt")
+    # inner dimensions, K below the kernel's floor, empty, unknown layout
+    assert not own_gemm_ok(z(m, k), z(n, k), "nn")
+    assert not own_gemm_ok(z(m, 32), z(n, 32), "nt")
+    assert not own_gemm_ok(z(0, k), z(n, k), "nt")
+    assert not own_gemm_ok(z(m, k), z(n, k), "tt")
+
+
+def test_linear_with_misaligned_weight_view_takes_the_library_path(no_kernel, monkeypatch):
+    from paddle_amd.ops import gemm_dispatch as gd
+    # a shape the table would give to the own kernel, on a "native" device
+    monkeypatch.setattr(gd, "_native_ok", lambda x: x.dtype == torch.bfloat16)
+    monkeypatch.setattr(gd, "use_own", lambda layout, m, n, k: True)
+    k, n = 64, 32
+    x = rn((4, k), 0, BF16)
+    parent = rn((k, n + 8), 1, BF16)
+    w = parent[:, 1:n + 1]                     # base 2 bytes off a 16-byte line
+    assert hot._own_linear_ok(x, parent[:, :n].contiguous())
+    assert not hot._own_linear_ok(x, w)
+    assert not hot._own_linear_ok(x[:, 1:], parent[1:, :n].contiguous())
+    bias = rn((n,), 2, BF16)
+    y = paddle.nn.functional.linear(x, w, bias)    # _Reached: no kernel, no raise
+    torch.testing.assert_close(y, torch.addmm(bias, x, w))

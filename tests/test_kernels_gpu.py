@@ -17,6 +17,8 @@ if torch.cuda.is_available():
 
     DEV = "cuda:0"
 
+from test_gemm_gpu import _gemm_rel_ok
+
 
 def _bf(x):
     return x.to(torch.bfloat16)
@@ -415,25 +417,6 @@ def test_flash_attention_gqa_bwd_gpu():
     _assert_close_bf16(v.grad, vf.grad, atol=8e-2, rtol=8e-2)
 
 
-# ---------------------------------------------------------------------------
-# gemm.hip: 8-phase MFMA GEMM, all layouts + epilogues (vs fp32 torch)
-# ---------------------------------------------------------------------------
-def _gemm_rel_ok(out, ref, tol=3e-2):
-    err = (out.float() - ref).abs().max().item() / max(ref.abs().max().item(), 1e-6)
-    assert err < tol, f"relerr {err:.3e}"
-
-
-@pytest.mark.parametrize("m,n,k", [(512, 512, 512), (768, 1024, 256),
-                                   (2048, 2048, 4096)])
-def test_gemm_nt_numerics(m, n, k):
-    torch.manual_seed(1)
-    C = _ext.get_ext()
-    a = _bf(torch.randn(m, k, device=DEV))
-    bt = _bf(torch.randn(n, k, device=DEV))
-    out = C.gemm_bf16_ex(a, bt, 0)[0]
-    _gemm_rel_ok(out, a.float() @ bt.float().t())
-
-
 def test_amax_abs():
     C = _ext.get_ext()
     for n in (999, 4096, 1 << 20):
@@ -443,145 +426,10 @@ def test_amax_abs():
         assert torch.allclose(out, ref), (float(out), float(ref))
 
 
-def test_gemm_fp8_batched_bias():
-    torch.manual_seed(7)
-    C = _ext.get_ext()
-    e, m, n, k = 8, 256, 512, 256
-    a = torch.randn(e, m, k, device=DEV).clamp(-2, 2)
-    bt = torch.randn(e, n, k, device=DEV).clamp(-2, 2)
-    bias = _bf(torch.randn(e, n, device=DEV))
-    qa = (a * 16).to(torch.float8_e4m3fn)
-    qb = (bt * 16).to(torch.float8_e4m3fn)
-    s = 1.0 / 256
-    out = C.gemm_fp8_nt_batched(qa, qb, s, bias)
-    ref = torch.einsum("emk,enk->emn", qa.float(), qb.float()) * s \
-        + bias.float().unsqueeze(1)
-    _gemm_rel_ok(out, ref, tol=5e-2)
-
-
-@pytest.mark.parametrize("e,m,n,k", [(4, 512, 512, 512), (8, 513, 1024, 4096),
-                                     (64, 513, 4096, 1024)])
-def test_gemm_nt_batched(e, m, n, k):
-    torch.manual_seed(2)
-    C = _ext.get_ext()
-    a = _bf(torch.randn(e, m, k, device=DEV))
-    bt = _bf(torch.randn(e, n, k, device=DEV))
-    out = C.gemm_bf16_nt_batched(a, bt)
-    ref = torch.einsum("emk,enk->emn", a.float(), bt.float())
-    _gemm_rel_ok(out, ref)
-
-
-@pytest.mark.parametrize("m,n,k", [(512, 512, 512), (2048, 1024, 2048)])
-def test_gemm_nn_numerics(m, n, k):
-    torch.manual_seed(2)
-    C = _ext.get_ext()
-    a = _bf(torch.randn(m, k, device=DEV))
-    b = _bf(torch.randn(k, n, device=DEV))
-    out = C.gemm_bf16_ex(a, b, 1)[0]
-    _gemm_rel_ok(out, a.float() @ b.float())
-
-
-@pytest.mark.parametrize("m,n,k", [(512, 512, 512), (1024, 2048, 2048)])
-def test_gemm_tn_numerics(m, n, k):
-    # wgrad: C[m,n] = At[k,m]^T @ B[k,n], reduction over k (the token dim)
-    torch.manual_seed(3)
-    C = _ext.get_ext()
-    at = _bf(torch.randn(k, m, device=DEV))
-    b = _bf(torch.randn(k, n, device=DEV))
-    out = C.gemm_bf16_ex(at, b, 2)[0]
-    _gemm_rel_ok(out, at.float().t() @ b.float(), tol=5e-2)
-
-
-def test_gemm_boundary_tiles():
-    # M/N not multiples of 256 exercise the guarded kernel + skip-interior
-    torch.manual_seed(4)
-    C = _ext.get_ext()
-    for (m, n, k) in [(300, 520, 512), (512, 777, 256), (130, 200, 128),
-                      (1000, 50304 % 2048 + 304, 512)]:
-        a = _bf(torch.randn(m, k, device=DEV))
-        bt = _bf(torch.randn(n, k, device=DEV))
-        out = C.gemm_bf16_ex(a, bt, 0)[0]
-        _gemm_rel_ok(out, a.float() @ bt.float().t())
-
-
-def test_gemm_k_tail():
-    # K not a multiple of 64: whole grid takes the guarded path
-    torch.manual_seed(5)
-    C = _ext.get_ext()
-    a = _bf(torch.randn(512, 200, device=DEV))
-    bt = _bf(torch.randn(512, 200, device=DEV))
-    out = C.gemm_bf16_ex(a, bt, 0)[0]
-    _gemm_rel_ok(out, a.float() @ bt.float().t())
-
-
-def test_gemm_bias_epilogue():
-    torch.manual_seed(6)
-    C = _ext.get_ext()
-    a = _bf(torch.randn(512, 512, device=DEV))
-    bt = _bf(torch.randn(768, 512, device=DEV))
-    bias = _bf(torch.randn(768, device=DEV))
-    out = C.gemm_bf16_ex(a, bt, 0, 1, bias)[0]
-    _gemm_rel_ok(out, a.float() @ bt.float().t() + bias.float())
-
-
-def test_gemm_bias_gelu_epilogue():
-    torch.manual_seed(7)
-    C = _ext.get_ext()
-    a = _bf(torch.randn(512, 512, device=DEV) * 0.5)
-    bt = _bf(torch.randn(768, 512, device=DEV) * 0.05)
-    bias = _bf(torch.randn(768, device=DEV) * 0.1)
-    out, aux = C.gemm_bf16_ex(a, bt, 0, 2, bias)
-    pre = a.float() @ bt.float().t() + bias.float()
-    _gemm_rel_ok(aux, pre)
-    _gemm_rel_ok(out, torch.nn.functional.gelu(pre), tol=4e-2)
-
-
-def test_gemm_dgelu_epilogue():
-    torch.manual_seed(8)
-    C = _ext.get_ext()
-    dy = _bf(torch.randn(512, 512, device=DEV))
-    w = _bf(torch.randn(768, 512, device=DEV) * 0.05)   # NT B-operand [n,k]
-    z = _bf(torch.randn(512, 768, device=DEV))          # saved pre-act
-    out = C.gemm_bf16_ex(dy, w, 0, 3, None, z)[0]       # [512, 768]
-    zf = z.float().requires_grad_(True)
-    torch.nn.functional.gelu(zf).backward(dy.float() @ w.float().t())
-    # out = (dy @ w^T) * gelu'(z)
-    _gemm_rel_ok(out, zf.grad, tol=5e-2)
-
-
-def test_gemm_accumulate():
-    torch.manual_seed(9)
-    C = _ext.get_ext()
-    at = _bf(torch.randn(512, 512, device=DEV))
-    b = _bf(torch.randn(512, 768, device=DEV))
-    c0 = _bf(torch.randn(512, 768, device=DEV))
-    acc = c0.clone()
-    C.gemm_bf16_ex(at, b, 2, 0, None, None, acc)
-    _gemm_rel_ok(acc, c0.float() + at.float().t() @ b.float(), tol=5e-2)
-
-
-def test_fused_linear_own_grads():
-    """fused_linear_own fwd+bwd vs fp32 autograd reference."""
-    from paddle_amd.ops import gemm_dispatch
-    torch.manual_seed(10)
-    m, k, n = 1024, 512, 768
-    x = _bf(torch.randn(2, m // 2, k, device=DEV)).requires_grad_(True)
-    w = (_bf(torch.randn(k, n, device=DEV)) * 0.05).requires_grad_(True)
-    bias = (_bf(torch.randn(n, device=DEV)) * 0.1).requires_grad_(True)
-    y = hot.fused_linear_own(x, w, bias)
-    loss = (y.float() ** 2).mean()
-    loss.backward()
-    xf = x.detach().float().requires_grad_(True)
-    wf = w.detach().float().requires_grad_(True)
-    bf_ = bias.detach().float().requires_grad_(True)
-    yf = xf @ wf + bf_
-    ((yf ** 2).mean()).backward()
-    _gemm_rel_ok(y, yf.detach(), tol=4e-2)
-    _gemm_rel_ok(x.grad, xf.grad, tol=5e-2)
-    _gemm_rel_ok(w.grad, wf.grad, tol=5e-2)
-    _gemm_rel_ok(bias.grad, bf_.grad, tol=5e-2)
-
-
+# ---------------------------------------------------------------------------
+# own-GEMM FFN pair and the transposed-weight cache (GEMM kernel tests:
+# test_gemm_gpu.py)
+# ---------------------------------------------------------------------------
 def test_fused_ffn_own_grads():
     torch.manual_seed(11)
     m, h, ffn = 512, 512, 1024
@@ -755,22 +603,6 @@ def test_fp8mx_probe_layout():
     _gemm_rel_ok(out, ref, tol=1e-3)
 
 
-@pytest.mark.parametrize("m,n,k", [(512, 512, 512), (777, 300, 256),
-                                   (2048, 1024, 4096)])
-def test_gemm_fp8_numerics(m, n, k):
-    torch.manual_seed(31)
-    C = _ext.get_ext()
-    a = (torch.randn(m, k, device=DEV) * 0.3).to(torch.float8_e4m3fn)
-    bt = (torch.randn(n, k, device=DEV) * 0.3).to(torch.float8_e4m3fn)
-    out = C.gemm_fp8_nt(a, bt, 0.731)
-    ref = 0.731 * (a.float() @ bt.float().t())
-    _gemm_rel_ok(out, ref, tol=2e-2)
-    # bias epilogue
-    bias = _bf(torch.randn(n, device=DEV))
-    outb = C.gemm_fp8_nt(a, bt, 1.0, bias)
-    _gemm_rel_ok(outb, a.float() @ bt.float().t() + bias.float(), tol=2e-2)
-
-
 def test_fp8_matmul_roundtrip():
     from paddle_amd.incubate import fp8
     torch.manual_seed(32)
@@ -843,24 +675,13 @@ def test_moe_gate_gradients_gpu():
 # ---------------------------------------------------------------------------
 # skinny decode GEMM (decode_gemm.hip)
 # ---------------------------------------------------------------------------
-@pytest.mark.parametrize("m,k,n", [(1, 4096, 4096), (16, 4096, 16384),
-                                   (32, 16384, 4096), (16, 4096, 50304),
-                                   (7, 2048, 1100)])
-def test_decode_gemm_numerics(m, k, n):
-    torch.manual_seed(50)
-    C = _ext.get_ext()
-    x = _bf(torch.randn(m, k, device=DEV))
-    w = _bf(torch.randn(k, n, device=DEV) * 0.02)
-    bias = _bf(torch.randn(n, device=DEV))
-    y = C.decode_gemm(x, w, bias)
-    ref = x.float() @ w.float() + bias.float()
-    _gemm_rel_ok(y, ref, tol=2e-2)
-    y2 = C.decode_gemm(x, w, None)
-    _gemm_rel_ok(y2, x.float() @ w.float(), tol=2e-2)
-
-
+# (1, 512, 256): M = 1, the min(row, M-1) row clamp; (32, 8192, 256): one N
+# block, so the split plan gives the most splits through the reduce;
+# (17, 256, 256): the first M that needs the second m-tile
 @pytest.mark.parametrize("m,k,n", [(32, 4096, 4096), (16, 512, 1024),
-                                   (5, 256, 512), (32, 4160, 12288)])
+                                   (5, 256, 512), (32, 4160, 12288),
+                                   (1, 512, 256), (32, 8192, 256),
+                                   (17, 256, 256)])
 def test_decode_gemm_mfma_numerics(m, k, n):
     torch.manual_seed(4)
     C = _ext.get_ext()

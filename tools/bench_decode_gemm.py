@@ -1,4 +1,4 @@
-"""Skinny decode GEMM bench: hipBLASLt vs own split-K vs own MFMA streamer.
+"""Skinny decode GEMM bench: hipBLASLt vs the own MFMA streamer.
 
 L3 is 256 MB, so re-timing ONE weight matrix measures L3-warm reads (the
 trap called out in profiles/serving_decode_analysis_r02.txt).  Each op is
@@ -23,10 +23,8 @@ for m, k, n in [(32, 4096, 12288), (32, 4096, 4096), (32, 4096, 16384),
     nw = max(2, int(1.6 / gb))          # >1.5 GB of distinct weights
     ws = [torch.randn(k, n, device="cuda", dtype=torch.bfloat16) * 0.02
           for _ in range(nw)]
-    t_own = bench(lambda i: C.decode_gemm(x, ws[i], None), nw)
     t_lt = bench(lambda i: torch.matmul(x, ws[i]), nw)
-    line = (f"M{m} K{k} N{n}: splitk {t_own*1e6:7.1f}us ({gb/t_own*1e-3:5.2f} TB/s)  "
-            f"lt {t_lt*1e6:7.1f}us ({gb/t_lt*1e-3:5.2f} TB/s)")
+    line = f"M{m} K{k} N{n}: lt {t_lt*1e6:7.1f}us ({gb/t_lt*1e-3:5.2f} TB/s)"
     if n % 256 == 0 and k % 64 == 0:
         t_mf = bench(lambda i: C.decode_gemm_mfma(x, ws[i], None), nw)
         line += f"  mfma {t_mf*1e6:7.1f}us ({gb/t_mf*1e-3:5.2f} TB/s)"
