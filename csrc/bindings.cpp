@@ -71,25 +71,29 @@ int dt_of(const Tensor& t) {
               #t " must be a contiguous fp32 GPU tensor with ", (n), " elements")
 
 // last-dim contract of the 8-wide row kernels
-static void check_rows(const Tensor& x, const char* op) {
+struct Rows { int64_t n, d; };
+static Rows check_rows(const Tensor& x, const char* op) {
   TORCH_CHECK(x.dim() >= 1 && x.numel() > 0, op, ": empty input");
   TORCH_CHECK(x.size(-1) % 8 == 0, op, ": D must be a multiple of 8");
+  return {x.numel() / x.size(-1), x.size(-1)};
+}
+
+static const void* opt_ptr(const c10::optional<Tensor>& t) {
+  return t.has_value() ? t->const_data_ptr() : nullptr;
 }
 
 // ---- norms ----------------------------------------------------------------
 std::vector<Tensor> layer_norm_fwd(const Tensor& x, const Tensor& w,
                                    const c10::optional<Tensor>& b, double eps) {
   CHECK_IN(x);
-  check_rows(x, "layer_norm");
-  int64_t d = x.size(-1), n = x.numel() / d;
+  auto [n, d] = check_rows(x, "layer_norm");
   CHECK_VEC(w, x, d);
   if (b.has_value()) CHECK_VEC((*b), x, d);
   auto y = torch::empty_like(x);
   auto mean = torch::empty({n}, x.options().dtype(torch::kFloat));
   auto rstd = torch::empty({n}, x.options().dtype(torch::kFloat));
   pa::layer_norm_fwd(x.const_data_ptr(), w.const_data_ptr(),
-                     b.has_value() ? b->const_data_ptr() : nullptr,
-                     y.mutable_data_ptr(), mean.mutable_data_ptr<float>(),
+                     opt_ptr(b), y.mutable_data_ptr(), mean.mutable_data_ptr<float>(),
                      rstd.mutable_data_ptr<float>(), n, d, (float)eps, dt_of(x),
                      cur_stream());
   return {y, mean, rstd};
@@ -101,8 +105,7 @@ std::vector<Tensor> add_layer_norm_fwd(const Tensor& x, const Tensor& residual,
                                        const Tensor& w,
                                        const c10::optional<Tensor>& b, double eps) {
   CHECK_IN(x);
-  check_rows(x, "add_layer_norm");
-  int64_t d = x.size(-1), n = x.numel() / d;
+  auto [n, d] = check_rows(x, "add_layer_norm");
   CHECK_SAME(residual, x);
   TORCH_CHECK(residual.sizes() == x.sizes(), "residual must have the shape of x");
   CHECK_VEC(w, x, d);
@@ -111,7 +114,7 @@ std::vector<Tensor> add_layer_norm_fwd(const Tensor& x, const Tensor& residual,
   auto y = torch::empty_like(x);
   auto mean = torch::empty({n}, x.options().dtype(torch::kFloat));
   auto rstd = torch::empty({n}, x.options().dtype(torch::kFloat));
-  const void* bp = b.has_value() ? b->const_data_ptr() : nullptr;
+  const void* bp = opt_ptr(b);
   if (pa::ln_fused_ok(d)) {
     pa::add_layer_norm_fwd(x.const_data_ptr(), residual.const_data_ptr(),
                            w.const_data_ptr(), bp, h.mutable_data_ptr(),
@@ -143,51 +146,45 @@ std::vector<Tensor> layer_norm_bwd(const Tensor& dy, const Tensor& x,
                                    const c10::optional<Tensor>& dres,
                                    bool fused, int64_t grid_cap) {
   CHECK_IN(x);
-  check_rows(x, "layer_norm_bwd");
-  int64_t d = x.size(-1), n = x.numel() / d;
+  auto [n, d] = check_rows(x, "layer_norm_bwd");
   CHECK_SAME(dy, x); CHECK_VEC(w, x, d);
   CHECK_STAT(mean, n); CHECK_STAT(rstd, n);
   if (dres.has_value()) CHECK_SAME((*dres), x);
   TORCH_CHECK(grid_cap >= 0 && grid_cap <= 65536, "layer_norm_bwd: bad grid_cap");
+  // dw/db stay fp32: the caller casts them to the parameter's dtype, which
+  // under amp O2 is fp32 next to bf16 activations
+  auto f32 = x.options().dtype(torch::kFloat);
+  auto dx = torch::empty_like(x);
+  auto dw = torch::empty({d}, f32);
+  auto db = torch::empty({d}, f32);
   if (fused && pa::ln_fused_ok(d)) {
-    auto dx = torch::empty_like(x);
-    auto dw = torch::empty({d}, x.options().dtype(torch::kFloat));
-    auto db = torch::empty({d}, x.options().dtype(torch::kFloat));
     int grid = pa::ln_bwd_fused_grid(n, (int)grid_cap);
-    auto ws = torch::empty({(int64_t)grid * 2 * d}, x.options().dtype(torch::kFloat));
+    auto ws = torch::empty({(int64_t)grid * 2 * d}, f32);
     pa::layer_norm_bwd_fused(dy.const_data_ptr(), x.const_data_ptr(),
                              w.const_data_ptr(), mean.const_data_ptr<float>(),
-                             rstd.const_data_ptr<float>(),
-                             dres.has_value() ? dres->const_data_ptr() : nullptr,
+                             rstd.const_data_ptr<float>(), opt_ptr(dres),
                              dx.mutable_data_ptr(), dw.mutable_data_ptr<float>(),
                              db.mutable_data_ptr<float>(),
                              ws.mutable_data_ptr<float>(), grid, n, d, dt_of(x),
                              cur_stream());
     return {dx, dw, db};
   }
-  auto dx = torch::empty_like(x);
-  auto dw = torch::zeros({d}, x.options().dtype(torch::kFloat));
-  auto db = torch::zeros({d}, x.options().dtype(torch::kFloat));
   pa::layer_norm_bwd_dx(dy.const_data_ptr(), x.const_data_ptr(), w.const_data_ptr(),
                         mean.const_data_ptr<float>(), rstd.const_data_ptr<float>(),
                         dx.mutable_data_ptr(), n, d, dt_of(x), cur_stream());
-  auto ws = torch::empty({(int64_t)2 * pa::ln_dwdb_chunks(n, d) * d},
-                         x.options().dtype(torch::kFloat));
+  auto ws = torch::empty({(int64_t)pa::col_chunks(n, d) * 2 * d}, f32);
   pa::layer_norm_bwd_dwdb(dy.const_data_ptr(), x.const_data_ptr(),
                           mean.const_data_ptr<float>(), rstd.const_data_ptr<float>(),
                           dw.mutable_data_ptr<float>(), db.mutable_data_ptr<float>(),
-                          n, d, dt_of(x), cur_stream(), ws.mutable_data_ptr<float>());
+                          ws.mutable_data_ptr<float>(), n, d, dt_of(x), cur_stream());
   if (dres.has_value()) dx.add_(dres->view_as(dx));
-  // dw/db stay fp32: the caller casts them to the parameter's dtype, which
-  // under amp O2 is fp32 next to bf16 activations
   return {dx, dw, db};
 }
 
 std::vector<Tensor> rms_norm_fwd(const Tensor& x, const c10::optional<Tensor>& residual,
                                  const Tensor& w, double eps) {
   CHECK_IN(x);
-  check_rows(x, "rms_norm");
-  int64_t d = x.size(-1), n = x.numel() / d;
+  auto [n, d] = check_rows(x, "rms_norm");
   CHECK_VEC(w, x, d);
   auto y = torch::empty_like(x);
   auto rstd = torch::empty({n}, x.options().dtype(torch::kFloat));
@@ -210,19 +207,18 @@ std::vector<Tensor> rms_norm_fwd(const Tensor& x, const c10::optional<Tensor>& r
 std::vector<Tensor> rms_norm_bwd(const Tensor& dy, const Tensor& x, const Tensor& w,
                                  const Tensor& rstd) {
   CHECK_IN(x);
-  check_rows(x, "rms_norm_bwd");
-  int64_t d = x.size(-1), n = x.numel() / d;
+  auto [n, d] = check_rows(x, "rms_norm_bwd");
   CHECK_SAME(dy, x); CHECK_VEC(w, x, d); CHECK_STAT(rstd, n);
+  auto f32 = x.options().dtype(torch::kFloat);
   auto dx = torch::empty_like(x);
-  auto dw = torch::zeros({d}, x.options().dtype(torch::kFloat));
+  auto dw = torch::empty({d}, f32);
   pa::rms_norm_bwd_dx(dy.const_data_ptr(), x.const_data_ptr(), w.const_data_ptr(),
                       rstd.const_data_ptr<float>(), dx.mutable_data_ptr(), n, d,
                       dt_of(x), cur_stream());
-  auto ws = torch::empty({(int64_t)2 * pa::ln_dwdb_chunks(n, d) * d},
-                         x.options().dtype(torch::kFloat));
+  auto ws = torch::empty({(int64_t)pa::col_chunks(n, d) * d}, f32);
   pa::rms_norm_bwd_dw(dy.const_data_ptr(), x.const_data_ptr(),
                       rstd.const_data_ptr<float>(), dw.mutable_data_ptr<float>(),
-                      n, d, dt_of(x), cur_stream(), ws.mutable_data_ptr<float>());
+                      ws.mutable_data_ptr<float>(), n, d, dt_of(x), cur_stream());
   return {dx, dw};  // fp32, cast by the caller
 }
 
@@ -261,26 +257,33 @@ Tensor softmax_ce_bwd(const Tensor& dloss, const Tensor& logits,
 // ---- elementwise ----------------------------------------------------------
 Tensor bias_gelu_fwd(const Tensor& x, const c10::optional<Tensor>& bias) {
   CHECK_IN(x);
-  check_rows(x, "bias_gelu");
-  int64_t d = x.size(-1), n = x.numel() / d;
+  auto [n, d] = check_rows(x, "bias_gelu");
   if (bias.has_value()) CHECK_VEC((*bias), x, d);
   auto y = torch::empty_like(x);
-  pa::bias_gelu_fwd(x.const_data_ptr(), bias.has_value() ? bias->const_data_ptr() : nullptr,
-                    y.mutable_data_ptr(), n, d, dt_of(x), cur_stream());
+  pa::bias_gelu_fwd(x.const_data_ptr(), opt_ptr(bias), y.mutable_data_ptr(), n, d,
+                    dt_of(x), cur_stream());
   return y;
 }
 
 Tensor bias_gelu_bwd(const Tensor& dy, const Tensor& x, const c10::optional<Tensor>& bias) {
   CHECK_IN(x);
-  check_rows(x, "bias_gelu_bwd");
-  int64_t d = x.size(-1), n = x.numel() / d;
+  auto [n, d] = check_rows(x, "bias_gelu_bwd");
   CHECK_SAME(dy, x);
   if (bias.has_value()) CHECK_VEC((*bias), x, d);
   auto dx = torch::empty_like(x);
-  pa::bias_gelu_bwd(dy.const_data_ptr(), x.const_data_ptr(),
-                    bias.has_value() ? bias->const_data_ptr() : nullptr,
+  pa::bias_gelu_bwd(dy.const_data_ptr(), x.const_data_ptr(), opt_ptr(bias),
                     dx.mutable_data_ptr(), n, d, dt_of(x), cur_stream());
   return dx;
+}
+
+Tensor colsum(const Tensor& x) {
+  CHECK_IN(x);
+  TORCH_CHECK(x.dim() >= 1 && x.numel() > 0, "colsum: empty input");
+  int64_t d = x.size(-1), n = x.numel() / d;
+  auto out = torch::zeros({d}, x.options().dtype(torch::kFloat));
+  pa::colsum(x.const_data_ptr(), out.mutable_data_ptr<float>(), n, d, dt_of(x),
+             cur_stream());
+  return out;
 }
 
 // {dx, db}: db fp32 [d] = column sum of dx as stored.  One kernel plus a
@@ -289,11 +292,10 @@ Tensor bias_gelu_bwd(const Tensor& dy, const Tensor& x, const c10::optional<Tens
 std::vector<Tensor> bias_gelu_bwd_db(const Tensor& dy, const Tensor& x,
                                      const c10::optional<Tensor>& bias, bool fused) {
   CHECK_IN(x);
-  check_rows(x, "bias_gelu_bwd_db");
-  int64_t d = x.size(-1), n = x.numel() / d;
+  auto [n, d] = check_rows(x, "bias_gelu_bwd_db");
   CHECK_SAME(dy, x);
   if (bias.has_value()) CHECK_VEC((*bias), x, d);
-  const void* bp = bias.has_value() ? bias->const_data_ptr() : nullptr;
+  const void* bp = opt_ptr(bias);
   auto dx = torch::empty_like(x);
   int grid = fused ? pa::bias_gelu_bwd_db_grid(n, d) : 0;
   if (grid > 0) {
@@ -308,10 +310,7 @@ std::vector<Tensor> bias_gelu_bwd_db(const Tensor& dy, const Tensor& x,
   }
   pa::bias_gelu_bwd(dy.const_data_ptr(), x.const_data_ptr(), bp,
                     dx.mutable_data_ptr(), n, d, dt_of(x), cur_stream());
-  auto db = torch::zeros({d}, x.options().dtype(torch::kFloat));
-  pa::colsum(dx.const_data_ptr(), db.mutable_data_ptr<float>(), n, d, dt_of(x),
-             cur_stream());
-  return {dx, db};
+  return {dx, colsum(dx)};
 }
 
 bool bias_gelu_bwd_db_fused(int64_t n, int64_t d) {
@@ -362,16 +361,6 @@ Tensor rope_fwd(const Tensor& x, const Tensor& cos_t, const Tensor& sin_t,
                sin_t.const_data_ptr<float>(), y.mutable_data_ptr(), b, sl, h, dh,
                pos_offset, conj, dt_of(x), cur_stream());
   return y;
-}
-
-Tensor colsum(const Tensor& x) {
-  CHECK_IN(x);
-  TORCH_CHECK(x.dim() >= 1 && x.numel() > 0, "colsum: empty input");
-  int64_t d = x.size(-1), n = x.numel() / d;
-  auto out = torch::zeros({d}, x.options().dtype(torch::kFloat));
-  pa::colsum(x.const_data_ptr(), out.mutable_data_ptr<float>(), n, d, dt_of(x),
-             cur_stream());
-  return out;
 }
 
 // ---- adamw ----------------------------------------------------------------
@@ -702,8 +691,7 @@ std::vector<Tensor> dropout_add_fwd(const Tensor& x, const c10::optional<Tensor>
     mask = torch::empty(x.sizes(), x.options().dtype(torch::kUInt8));
     maskp = mask.mutable_data_ptr<uint8_t>();
   }
-  pa::dropout_add_fwd(x.const_data_ptr(),
-                      residual.has_value() ? residual->const_data_ptr() : nullptr,
+  pa::dropout_add_fwd(x.const_data_ptr(), opt_ptr(residual),
                       y.mutable_data_ptr(), maskp, x.numel(), (float)p,
                       (uint64_t)seed, (uint64_t)offset, dt_of(x), cur_stream());
   if (p > 0) return {y, mask};

@@ -6,8 +6,7 @@
 // HBM-bound at ~8 TB/s.  Replaces the reference's per-param
 // adamw_kernel.cu + multi_tensor_apply.h (fused_adam_kernel.cu) -- the
 // flat-shard layout makes multi-tensor machinery unnecessary.
-#include "common.h"
-#include "api.h"
+#include "row_io.h"
 
 namespace pa {
 
@@ -86,21 +85,13 @@ void adamw(float* master, void* param_bf16, const void* grad, float* m,
   float bias1 = 1.f - beta1_pow;
   float bias2 = 1.f - beta2_pow;
   dim3 g((unsigned)elementwise_grid(cdiv((int)hmin<int64_t>(numel / 8 + 1, 1 << 30), 256)));
-  if (grad_dtype == kBF16) {
-    if (param_out_bf16)
-      hipLaunchKernelGGL((adamw_kernel<kBF16, true>), g, dim3(256), 0, s, master,
-                         param_bf16, grad, m, v, numel, lr, beta1, beta2, eps, wd, bias1, bias2, grad_scale);
-    else
-      hipLaunchKernelGGL((adamw_kernel<kBF16, false>), g, dim3(256), 0, s, master,
-                         param_bf16, grad, m, v, numel, lr, beta1, beta2, eps, wd, bias1, bias2, grad_scale);
-  } else {
-    if (param_out_bf16)
-      hipLaunchKernelGGL((adamw_kernel<kF32, true>), g, dim3(256), 0, s, master,
-                         param_bf16, grad, m, v, numel, lr, beta1, beta2, eps, wd, bias1, bias2, grad_scale);
-    else
-      hipLaunchKernelGGL((adamw_kernel<kF32, false>), g, dim3(256), 0, s, master,
-                         param_bf16, grad, m, v, numel, lr, beta1, beta2, eps, wd, bias1, bias2, grad_scale);
-  }
+  by_dtype(grad_dtype, [&](auto GDT) {
+    by_flag(param_out_bf16, [&](auto BF16OUT) {
+      hipLaunchKernelGGL((adamw_kernel<GDT(), BF16OUT()>), g, dim3(256), 0, s, master,
+                         param_bf16, grad, m, v, numel, lr, beta1, beta2, eps, wd,
+                         bias1, bias2, grad_scale);
+    });
+  });
 }
 
 template <int DT>
@@ -134,10 +125,9 @@ __global__ void l2norm_sq_kernel(const void* __restrict__ x, float* __restrict__
 
 void l2norm_sq(const void* x, float* out, int64_t numel, int dtype, hipStream_t s) {
   dim3 g((unsigned)elementwise_grid(cdiv((int)hmin<int64_t>(numel / 4 + 1, 1 << 30), 256)));
-  if (dtype == kBF16)
-    hipLaunchKernelGGL((l2norm_sq_kernel<kBF16>), g, dim3(256), 0, s, x, out, numel);
-  else
-    hipLaunchKernelGGL((l2norm_sq_kernel<kF32>), g, dim3(256), 0, s, x, out, numel);
+  by_dtype(dtype, [&](auto DT) {
+    hipLaunchKernelGGL((l2norm_sq_kernel<DT()>), g, dim3(256), 0, s, x, out, numel);
+  });
 }
 
 }  // namespace pa

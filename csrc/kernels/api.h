@@ -17,11 +17,18 @@ void layer_norm_fwd(const void* x, const void* w, const void* b, void* y,
 void layer_norm_bwd_dx(const void* dy, const void* x, const void* w,
                        const float* mean, const float* rstd, void* dx,
                        int64_t n, int64_t d, int dtype, hipStream_t s);
-int ln_dwdb_chunks(int64_t n, int64_t d);
+// dw / db of the two-kernel backward, d % 8 == 0.  One column walk writes
+// per-chunk partials to ws, fp32 [col_chunks(n, d)][nout][d] with nout = 2
+// (layer_norm_bwd_dwdb: dw and db, db may be null) or 1 (rms_norm_bwd_dw), and
+// ws_reduce adds them in a fixed order: ws and the outputs need no
+// initialisation.  col_chunks is also the row-chunk count of colsum's grid.
+int col_chunks(int64_t n, int64_t d);
 void layer_norm_bwd_dwdb(const void* dy, const void* x, const float* mean,
-                         const float* rstd, float* dw, float* db, int64_t n,
-                         int64_t d, int dtype, hipStream_t s,
-                         float* ws = nullptr);
+                         const float* rstd, float* dw, float* db, float* ws,
+                         int64_t n, int64_t d, int dtype, hipStream_t s);
+void rms_norm_bwd_dw(const void* dy, const void* x, const float* rstd,
+                     float* dw, float* ws, int64_t n, int64_t d, int dtype,
+                     hipStream_t s);
 
 // Register-resident fused norms (d % 8 == 0, d <= kLnFusedMaxD).
 constexpr int64_t kLnFusedMaxD = 8192;
@@ -52,9 +59,6 @@ void rms_norm_fwd(const void* x, const void* residual, const void* w, void* y,
 void rms_norm_bwd_dx(const void* dy, const void* x, const void* w,
                      const float* rstd, void* dx, int64_t n, int64_t d,
                      int dtype, hipStream_t s);
-void rms_norm_bwd_dw(const void* dy, const void* x, const float* rstd,
-                     float* dw, int64_t n, int64_t d, int dtype, hipStream_t s,
-                     float* ws = nullptr);
 
 // ---- fused softmax cross-entropy ------------------------------------------
 // logits [n, v]; labels int64 [n]; loss/lse fp32 [n]
@@ -71,7 +75,7 @@ void softmax_ce_bwd(const float* dloss, const void* logits,
 // y = gelu(x + bias); bias [d] may be null
 void bias_gelu_fwd(const void* x, const void* bias, void* y, int64_t n,
                    int64_t d, int dtype, hipStream_t s);
-// dx = gelu'(x+bias) * dy  (dbias reduced by caller or dwdb-style kernel)
+// dx = gelu'(x+bias) * dy  (the bias gradient: bias_gelu_bwd_db, or colsum of dx)
 void bias_gelu_bwd(const void* dy, const void* x, const void* bias, void* dx,
                    int64_t n, int64_t d, int dtype, hipStream_t s);
 // Same dx, plus db[d] = colsum(dx as stored) from per-thread partials.
@@ -95,8 +99,10 @@ void rope_fwd(const void* x, const float* cos_t, const float* sin_t, void* y,
               int64_t b, int64_t sl, int64_t h, int64_t dh, int64_t pos_offset,
               bool conj, int dtype, hipStream_t s);
 
-// column-sum of [n, d] into fp32 [d] (bias grads)
+// out[0] = max |x| over a flat buffer (atomic max into a zeroed fp32)
 void amax_abs(const void* x, float* out, int64_t n, int dtype, hipStream_t s);
+// column-sum of [n, d], any d, added into a zeroed fp32 [d] by atomics (bias
+// grads): the last bits depend on dispatch order
 void colsum(const void* x, float* out, int64_t n, int64_t d, int dtype,
             hipStream_t s);
 

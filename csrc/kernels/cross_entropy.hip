@@ -6,48 +6,9 @@
 //
 // Reference behavior parity: paddle/phi/kernels/gpu/cross_entropy_kernel.cu
 // (VectorizedSoftmaxForward / WarpSoftmaxForward) -- re-derived for wave64.
-#include "common.h"
-#include "api.h"
+#include "row_io.h"
 
 namespace pa {
-
-template <int DT> struct VIO2;
-template <> struct VIO2<kBF16> {
-  static __device__ __forceinline__ void load8(const void* p, int64_t idx, float* f) {
-    shortx8 v = *reinterpret_cast<const shortx8*>((const short*)p + idx);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) f[i] = bf2f(v[i]);
-  }
-  static __device__ __forceinline__ void store8(void* p, int64_t idx, const float* f) {
-    shortx8 v;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) v[i] = f2bf(f[i]);
-    *reinterpret_cast<shortx8*>((short*)p + idx) = v;
-  }
-  static __device__ __forceinline__ float load1(const void* p, int64_t idx) {
-    return bf2f(((const short*)p)[idx]);
-  }
-  static __device__ __forceinline__ void store1(void* p, int64_t idx, float f) {
-    ((short*)p)[idx] = f2bf(f);
-  }
-};
-template <> struct VIO2<kF32> {
-  static __device__ __forceinline__ void load8(const void* p, int64_t idx, float* f) {
-    const float4* q = reinterpret_cast<const float4*>((const float*)p + idx);
-    float4 a = q[0], b = q[1];
-    f[0]=a.x; f[1]=a.y; f[2]=a.z; f[3]=a.w; f[4]=b.x; f[5]=b.y; f[6]=b.z; f[7]=b.w;
-  }
-  static __device__ __forceinline__ void store8(void* p, int64_t idx, const float* f) {
-    float4* q = reinterpret_cast<float4*>((float*)p + idx);
-    q[0] = make_float4(f[0],f[1],f[2],f[3]); q[1] = make_float4(f[4],f[5],f[6],f[7]);
-  }
-  static __device__ __forceinline__ float load1(const void* p, int64_t idx) {
-    return ((const float*)p)[idx];
-  }
-  static __device__ __forceinline__ void store1(void* p, int64_t idx, float f) {
-    ((float*)p)[idx] = f;
-  }
-};
 
 // Running maximum of a lane that has seen nothing yet.  It is the largest
 // finite negative float, not -inf: a -inf logit (a banned token) that arrives
@@ -85,13 +46,13 @@ __global__ void ce_fwd_kernel(const void* __restrict__ logits,
     const int64_t v8 = v & ~7LL;
     for (; i < v8; i += blockDim.x * 8) {
       float f[8];
-      VIO2<DT>::load8(logits, base + i, f);
+      VIO<DT>::load8(logits, base + i, f);
 #pragma unroll
       for (int k = 0; k < 8; ++k) lse_step(m, l, f[k]);
     }
     // tail
     for (int64_t j = v8 + threadIdx.x; j < v; j += blockDim.x) {
-      lse_step(m, l, VIO2<DT>::load1(logits, base + j));
+      lse_step(m, l, VIO<DT>::load1(logits, base + j));
     }
     // wave reduce
 #pragma unroll
@@ -115,7 +76,7 @@ __global__ void ce_fwd_kernel(const void* __restrict__ logits,
       if (lab == ignore_index || lab < 0 || lab >= v) {
         loss[row] = 0.f;
       } else {
-        float xl = VIO2<DT>::load1(logits, base + lab);
+        float xl = VIO<DT>::load1(logits, base + lab);
         loss[row] = lse - xl;
       }
     }
@@ -138,17 +99,17 @@ __global__ void ce_bwd_kernel(const float* __restrict__ dloss,
     int64_t i = threadIdx.x * 8;
     for (; i < v8; i += blockDim.x * 8) {
       float f[8];
-      VIO2<DT>::load8(logits, base + i, f);
+      VIO<DT>::load8(logits, base + i, f);
 #pragma unroll
       for (int k = 0; k < 8; ++k) {
         float p = __expf(f[k] - ls);
         f[k] = g * (p - ((i + k) == lab ? 1.f : 0.f));
       }
-      VIO2<DT>::store8(dlogits, base + i, f);
+      VIO<DT>::store8(dlogits, base + i, f);
     }
     for (int64_t j = v8 + threadIdx.x; j < v; j += blockDim.x) {
-      float p = __expf(VIO2<DT>::load1(logits, base + j) - ls);
-      VIO2<DT>::store1(dlogits, base + j, g * (p - (j == lab ? 1.f : 0.f)));
+      float p = __expf(VIO<DT>::load1(logits, base + j) - ls);
+      VIO<DT>::store1(dlogits, base + j, g * (p - (j == lab ? 1.f : 0.f)));
     }
   }
 }
@@ -157,12 +118,10 @@ void softmax_ce_fwd(const void* logits, const int64_t* labels, float* loss,
                     float* lse, int64_t n, int64_t v, int64_t ignore_index,
                     int dtype, hipStream_t s) {
   int grid = (int)(n < 2048 ? n : 2048);
-  if (dtype == kBF16)
-    hipLaunchKernelGGL((ce_fwd_kernel<kBF16>), dim3(grid), dim3(256), 0, s,
+  by_dtype(dtype, [&](auto DT) {
+    hipLaunchKernelGGL((ce_fwd_kernel<DT()>), dim3(grid), dim3(256), 0, s,
                        logits, labels, loss, lse, n, v, ignore_index);
-  else
-    hipLaunchKernelGGL((ce_fwd_kernel<kF32>), dim3(grid), dim3(256), 0, s,
-                       logits, labels, loss, lse, n, v, ignore_index);
+  });
 }
 
 void softmax_ce_bwd(const float* dloss, const void* logits,
@@ -170,12 +129,10 @@ void softmax_ce_bwd(const float* dloss, const void* logits,
                     int64_t n, int64_t v, int64_t ignore_index, int dtype,
                     hipStream_t s) {
   int grid = (int)(n < 2048 ? n : 2048);
-  if (dtype == kBF16)
-    hipLaunchKernelGGL((ce_bwd_kernel<kBF16>), dim3(grid), dim3(256), 0, s,
+  by_dtype(dtype, [&](auto DT) {
+    hipLaunchKernelGGL((ce_bwd_kernel<DT()>), dim3(grid), dim3(256), 0, s,
                        dloss, logits, labels, lse, dlogits, n, v, ignore_index);
-  else
-    hipLaunchKernelGGL((ce_bwd_kernel<kF32>), dim3(grid), dim3(256), 0, s,
-                       dloss, logits, labels, lse, dlogits, n, v, ignore_index);
+  });
 }
 
 }  // namespace pa

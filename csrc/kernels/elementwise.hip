@@ -1,40 +1,13 @@
 // Fused elementwise kernels: bias+gelu, swiglu, rope, dropout+residual,
-// column-sum -- all HBM-bound, vectorized 8-wide, grid-stride.
+// column-sum, |x| max -- all HBM-bound, vectorized 8-wide, grid-stride.
 //
 // Reference behavior parity: paddle/phi/kernels/fusion/gpu/
 // fused_bias_act_kernel.cu, fused_dropout_add_kernel.cu,
 // fused_rope_kernel.cu (RotateHalf) -- re-derived for wave64/CDNA4
 // (guide Appendix B: trig tables precomputed on host, never on-device).
-#include "common.h"
-#include "api.h"
+#include "row_io.h"
 
 namespace pa {
-
-template <int DT> struct LS8;
-template <> struct LS8<kBF16> {
-  static __device__ __forceinline__ void load8(const void* p, int64_t idx, float* f) {
-    shortx8 v = *reinterpret_cast<const shortx8*>((const short*)p + idx);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) f[i] = bf2f(v[i]);
-  }
-  static __device__ __forceinline__ void store8(void* p, int64_t idx, const float* f) {
-    shortx8 v;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) v[i] = f2bf(f[i]);
-    *reinterpret_cast<shortx8*>((short*)p + idx) = v;
-  }
-};
-template <> struct LS8<kF32> {
-  static __device__ __forceinline__ void load8(const void* p, int64_t idx, float* f) {
-    const float4* q = reinterpret_cast<const float4*>((const float*)p + idx);
-    float4 a = q[0], b = q[1];
-    f[0]=a.x; f[1]=a.y; f[2]=a.z; f[3]=a.w; f[4]=b.x; f[5]=b.y; f[6]=b.z; f[7]=b.w;
-  }
-  static __device__ __forceinline__ void store8(void* p, int64_t idx, const float* f) {
-    float4* q = reinterpret_cast<float4*>((float*)p + idx);
-    q[0] = make_float4(f[0],f[1],f[2],f[3]); q[1] = make_float4(f[4],f[5],f[6],f[7]);
-  }
-};
 
 // erf via Abramowitz-Stegun 7.1.26 (|err| < 1.5e-7, far below bf16 ulp):
 // libm erff expands to ~60 VALU ops with branch blends, which made the
@@ -93,9 +66,9 @@ __global__ void bias_gelu_kernel(const void* __restrict__ a, const void* __restr
     float xf[W], bf[W], af[W];
 #pragma unroll
     for (int v8 = 0; v8 < W / 8; ++v8) {
-      LS8<DT>::load8(x, i + 8 * v8, xf + 8 * v8);
-      if (bias) LS8<DT>::load8(bias, c + 8 * v8, bf + 8 * v8);
-      if (!FWD) LS8<DT>::load8(a, i + 8 * v8, af + 8 * v8);
+      VIO<DT>::load8(x, i + 8 * v8, xf + 8 * v8);
+      if (bias) VIO<DT>::load8(bias, c + 8 * v8, bf + 8 * v8);
+      if (!FWD) VIO<DT>::load8(a, i + 8 * v8, af + 8 * v8);
     }
 #pragma unroll
     for (int k = 0; k < W; ++k) {
@@ -105,12 +78,12 @@ __global__ void bias_gelu_kernel(const void* __restrict__ a, const void* __restr
     }
 #pragma unroll
     for (int v8 = 0; v8 < W / 8; ++v8)
-      LS8<DT>::store8(out, i + 8 * v8, xf + 8 * v8);
+      VIO<DT>::store8(out, i + 8 * v8, xf + 8 * v8);
   }
   if (BGRAD) {
 #pragma unroll
     for (int v8 = 0; v8 < W / 8; ++v8)
-      LS8<kF32>::store8(ws, i0 + 8 * v8, acc + 8 * v8);
+      VIO<kF32>::store8(ws, i0 + 8 * v8, acc + 8 * v8);
   }
 }
 
@@ -122,11 +95,11 @@ __global__ void swiglu_fwd_kernel(const void* __restrict__ x, void* __restrict__
        i += (int64_t)gridDim.x * blockDim.x * 8) {
     int64_t row = i / d, col = i % d;
     float g[8], u[8];
-    LS8<DT>::load8(x, row * 2 * d + col, g);
-    LS8<DT>::load8(x, row * 2 * d + d + col, u);
+    VIO<DT>::load8(x, row * 2 * d + col, g);
+    VIO<DT>::load8(x, row * 2 * d + d + col, u);
 #pragma unroll
     for (int k = 0; k < 8; ++k) g[k] = silu_f(g[k]) * u[k];
-    LS8<DT>::store8(y, i, g);
+    VIO<DT>::store8(y, i, g);
   }
 }
 
@@ -138,16 +111,16 @@ __global__ void swiglu_bwd_kernel(const void* __restrict__ dy, const void* __res
        i += (int64_t)gridDim.x * blockDim.x * 8) {
     int64_t row = i / d, col = i % d;
     float g[8], u[8], dyf[8], dg[8];
-    LS8<DT>::load8(x, row * 2 * d + col, g);
-    LS8<DT>::load8(x, row * 2 * d + d + col, u);
-    LS8<DT>::load8(dy, i, dyf);
+    VIO<DT>::load8(x, row * 2 * d + col, g);
+    VIO<DT>::load8(x, row * 2 * d + d + col, u);
+    VIO<DT>::load8(dy, i, dyf);
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
       dg[k] = dyf[k] * u[k] * silu_grad_f(g[k]);
       u[k] = dyf[k] * silu_f(g[k]);  // du
     }
-    LS8<DT>::store8(dx, row * 2 * d + col, dg);
-    LS8<DT>::store8(dx, row * 2 * d + d + col, u);
+    VIO<DT>::store8(dx, row * 2 * d + col, dg);
+    VIO<DT>::store8(dx, row * 2 * d + d + col, u);
   }
 }
 
@@ -207,7 +180,9 @@ __global__ void rope_kernel(const void* __restrict__ x, const float* __restrict_
 }
 
 // column-sum [n, d] -> fp32 [d].  8-wide column strips per thread (16 B
-// loads) instead of scalar b16 loads; 2-D grid tiles rows.
+// loads) when d % 8 == 0, else the strip's columns one by one (rows are then
+// off the 16-byte grid); 2-D grid tiles rows, one fp32 atomic per (column,
+// row chunk) into a zeroed output.
 template <int DT>
 __global__ void colsum_kernel(const void* __restrict__ x, float* __restrict__ out,
                               int64_t n, int64_t d) {
@@ -216,18 +191,18 @@ __global__ void colsum_kernel(const void* __restrict__ x, float* __restrict__ ou
   int64_t rows_per = (n + gridDim.y - 1) / gridDim.y;
   int64_t r0 = (int64_t)blockIdx.y * rows_per, r1 = min(n, r0 + rows_per);
   float acc[8] = {0.f};
-  if (c0 + 8 <= d) {
+  if (d % 8 == 0) {
     for (int64_t r = r0; r < r1; ++r) {
       float v[8];
-      LS8<DT>::load8(x, r * d + c0, v);
+      VIO<DT>::load8(x, r * d + c0, v);
 #pragma unroll
       for (int k = 0; k < 8; ++k) acc[k] += v[k];
     }
   } else {
     for (int64_t r = r0; r < r1; ++r)
-      for (int64_t c = c0; c < d; ++c)
-        acc[c - c0] += (DT == kBF16) ? bf2f(((const short*)x)[r * d + c])
-                                     : ((const float*)x)[r * d + c];
+#pragma unroll
+      for (int k = 0; k < 8; ++k)
+        if (c0 + k < d) acc[k] += VIO<DT>::load1(x, r * d + c0 + k);
   }
 #pragma unroll
   for (int k = 0; k < 8; ++k)
@@ -252,8 +227,8 @@ __global__ void dropout_add_fwd_kernel(const void* __restrict__ x, const void* _
   for (int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 8; i < numel;
        i += (int64_t)gridDim.x * blockDim.x * 8) {
     float xf[8], rf[8];
-    LS8<DT>::load8(x, i, xf);
-    if (res) LS8<DT>::load8(res, i, rf);
+    VIO<DT>::load8(x, i, xf);
+    if (res) VIO<DT>::load8(res, i, rf);
     uchar2 mk[4];
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
@@ -262,7 +237,7 @@ __global__ void dropout_add_fwd_kernel(const void* __restrict__ x, const void* _
       xf[k] = (keep ? xf[k] * scale_ : 0.f) + (res ? rf[k] : 0.f);
     }
     if (mask) *reinterpret_cast<uint2*>(mask + i) = *reinterpret_cast<uint2*>(mk);
-    LS8<DT>::store8(y, i, xf);
+    VIO<DT>::store8(y, i, xf);
   }
 }
 
@@ -273,143 +248,13 @@ __global__ void dropout_add_bwd_kernel(const void* __restrict__ dy, const uint8_
   for (int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 8; i < numel;
        i += (int64_t)gridDim.x * blockDim.x * 8) {
     float f[8];
-    LS8<DT>::load8(dy, i, f);
+    VIO<DT>::load8(dy, i, f);
 #pragma unroll
     for (int k = 0; k < 8; ++k) f[k] = mask[i + k] ? f[k] * scale_ : 0.f;
-    LS8<DT>::store8(dx, i, f);
+    VIO<DT>::store8(dx, i, f);
   }
 }
 
-// ---- host launchers -------------------------------------------------------
-#define EDT(dtype, KERNEL_CALL_BF16, KERNEL_CALL_F32) \
-  if (dtype == kBF16) { KERNEL_CALL_BF16; } else { KERNEL_CALL_F32; }
-
-static dim3 egrid(int64_t numel) {
-  return dim3((unsigned)elementwise_grid(cdiv((int)hmin<int64_t>(numel / 8 + 1, 1 << 30), 256)));
-}
-
-void bias_gelu_fwd(const void* x, const void* bias, void* y, int64_t n,
-                   int64_t d, int dtype, hipStream_t s) {
-  if (d % 16 == 0) {
-    dim3 g = egrid(n * d / 2);
-    EDT(dtype,
-        hipLaunchKernelGGL((bias_gelu_kernel<kBF16, true, 16>), g, dim3(256), 0, s, x, x, bias, y, n, d),
-        hipLaunchKernelGGL((bias_gelu_kernel<kF32, true, 16>), g, dim3(256), 0, s, x, x, bias, y, n, d));
-  } else {
-    dim3 g = egrid(n * d);
-    EDT(dtype,
-        hipLaunchKernelGGL((bias_gelu_kernel<kBF16, true, 8>), g, dim3(256), 0, s, x, x, bias, y, n, d),
-        hipLaunchKernelGGL((bias_gelu_kernel<kF32, true, 8>), g, dim3(256), 0, s, x, x, bias, y, n, d));
-  }
-}
-
-void bias_gelu_bwd(const void* dy, const void* x, const void* bias, void* dx,
-                   int64_t n, int64_t d, int dtype, hipStream_t s) {
-  if (d % 16 == 0) {
-    dim3 g = egrid(n * d / 2);
-    EDT(dtype,
-        hipLaunchKernelGGL((bias_gelu_kernel<kBF16, false, 16>), g, dim3(256), 0, s, dy, x, bias, dx, n, d),
-        hipLaunchKernelGGL((bias_gelu_kernel<kF32, false, 16>), g, dim3(256), 0, s, dy, x, bias, dx, n, d));
-  } else {
-    dim3 g = egrid(n * d);
-    EDT(dtype,
-        hipLaunchKernelGGL((bias_gelu_kernel<kBF16, false, 8>), g, dim3(256), 0, s, dy, x, bias, dx, n, d),
-        hipLaunchKernelGGL((bias_gelu_kernel<kF32, false, 8>), g, dim3(256), 0, s, dy, x, bias, dx, n, d));
-  }
-}
-
-// Grid of the backward with the bias gradient fused: the smallest multiple
-// of q = d / gcd(d, 256*W) blocks that covers the elementwise grid, within
-// the elementwise cap (else the largest multiple below the cap).  0: no such
-// grid, the caller runs bias_gelu_bwd followed by colsum.
-static int64_t gcd64(int64_t a, int64_t b) { while (b) { int64_t t = a % b; a = b; b = t; } return a; }
-
-int bias_gelu_bwd_db_grid(int64_t n, int64_t d) {
-  if (d % 8 != 0 || n <= 0) return 0;
-  const int W = d % 16 == 0 ? 16 : 8;
-  const int64_t cap = elementwise_grid(1LL << 40);
-  const int64_t g0 = egrid(n * d / (W / 8)).x;
-  const int64_t q = d / gcd64(d, 256 * W);
-  if (q > cap) return 0;
-  int64_t g = (g0 + q - 1) / q * q;
-  if (g > cap) g = cap / q * q;
-  return (int)g;
-}
-
-void bias_gelu_bwd_db(const void* dy, const void* x, const void* bias, void* dx,
-                      float* db, float* ws, int grid, int64_t n, int64_t d,
-                      int dtype, hipStream_t s) {
-  dim3 g((unsigned)grid);
-  if (d % 16 == 0) {
-    EDT(dtype,
-        hipLaunchKernelGGL((bias_gelu_kernel<kBF16, false, 16, true>), g, dim3(256), 0, s, dy, x, bias, dx, n, d, ws),
-        hipLaunchKernelGGL((bias_gelu_kernel<kF32, false, 16, true>), g, dim3(256), 0, s, dy, x, bias, dx, n, d, ws));
-    ws_reduce(ws, db, nullptr, (int)((int64_t)grid * 256 * 16 / d), 1, d, s);
-  } else {
-    EDT(dtype,
-        hipLaunchKernelGGL((bias_gelu_kernel<kBF16, false, 8, true>), g, dim3(256), 0, s, dy, x, bias, dx, n, d, ws),
-        hipLaunchKernelGGL((bias_gelu_kernel<kF32, false, 8, true>), g, dim3(256), 0, s, dy, x, bias, dx, n, d, ws));
-    ws_reduce(ws, db, nullptr, (int)((int64_t)grid * 256 * 8 / d), 1, d, s);
-  }
-}
-
-void swiglu_fwd(const void* x, void* y, int64_t n, int64_t d, int dtype, hipStream_t s) {
-  dim3 g = egrid(n * d);
-  EDT(dtype,
-      hipLaunchKernelGGL((swiglu_fwd_kernel<kBF16>), g, dim3(256), 0, s, x, y, n, d),
-      hipLaunchKernelGGL((swiglu_fwd_kernel<kF32>), g, dim3(256), 0, s, x, y, n, d));
-}
-
-void swiglu_bwd(const void* dy, const void* x, void* dx, int64_t n, int64_t d,
-                int dtype, hipStream_t s) {
-  dim3 g = egrid(n * d);
-  EDT(dtype,
-      hipLaunchKernelGGL((swiglu_bwd_kernel<kBF16>), g, dim3(256), 0, s, dy, x, dx, n, d),
-      hipLaunchKernelGGL((swiglu_bwd_kernel<kF32>), g, dim3(256), 0, s, dy, x, dx, n, d));
-}
-
-void rope_fwd(const void* x, const float* cos_t, const float* sin_t, void* y,
-              int64_t b, int64_t sl, int64_t h, int64_t dh, int64_t pos_offset,
-              bool conj, int dtype, hipStream_t s) {
-  int64_t rows = b * sl * h;
-  dim3 g((unsigned)hmin<int64_t>(cdiv((int)hmin<int64_t>(rows, 1 << 24), 4), 2048));
-  float ssign = conj ? -1.f : 1.f;
-  EDT(dtype,
-      hipLaunchKernelGGL((rope_kernel<kBF16>), g, dim3(256), 0, s, x, cos_t, sin_t, y, b, sl, h, dh, pos_offset, ssign),
-      hipLaunchKernelGGL((rope_kernel<kF32>), g, dim3(256), 0, s, x, cos_t, sin_t, y, b, sl, h, dh, pos_offset, ssign));
-}
-
-void colsum(const void* x, float* out, int64_t n, int64_t d, int dtype, hipStream_t s) {
-  int xblocks = cdiv((int)d, 256 * 8);
-  // keep >=1024 workgroups in flight (256 CUs / 8 XCDs want oversubscription)
-  int chunks = (int)hmin<int64_t>(hmax<int64_t>(1, n / 32),
-                                  hmax<int64_t>(1, 2048 / xblocks));
-  dim3 grid((unsigned)xblocks, chunks);
-  EDT(dtype,
-      hipLaunchKernelGGL((colsum_kernel<kBF16>), grid, dim3(256), 0, s, x, out, n, d),
-      hipLaunchKernelGGL((colsum_kernel<kF32>), grid, dim3(256), 0, s, x, out, n, d));
-}
-
-void dropout_add_fwd(const void* x, const void* residual, void* y,
-                     uint8_t* mask, int64_t numel, float p, uint64_t seed,
-                     uint64_t offset, int dtype, hipStream_t s) {
-  dim3 g = egrid(numel);
-  EDT(dtype,
-      hipLaunchKernelGGL((dropout_add_fwd_kernel<kBF16>), g, dim3(256), 0, s, x, residual, y, mask, numel, p, seed, offset),
-      hipLaunchKernelGGL((dropout_add_fwd_kernel<kF32>), g, dim3(256), 0, s, x, residual, y, mask, numel, p, seed, offset));
-}
-
-void dropout_add_bwd(const void* dy, const uint8_t* mask, void* dx,
-                     int64_t numel, float p, int dtype, hipStream_t s) {
-  dim3 g = egrid(numel);
-  EDT(dtype,
-      hipLaunchKernelGGL((dropout_add_bwd_kernel<kBF16>), g, dim3(256), 0, s, dy, mask, dx, numel, p),
-      hipLaunchKernelGGL((dropout_add_bwd_kernel<kF32>), g, dim3(256), 0, s, dy, mask, dx, numel, p));
-}
-
-}  // namespace pa
-
-namespace pa {
 // ---------------------------------------------------------------------------
 // fused |x| max: single read pass (x.abs().amax() materializes |x| and
 // re-reads it -- 3x the traffic; this is the fp8 quantize-scale producer)
@@ -422,7 +267,7 @@ __global__ void amax_abs_kernel(const void* __restrict__ x, float* __restrict__ 
   int64_t stride = (int64_t)gridDim.x * blockDim.x * 8;
   for (int64_t i = i0; i + 8 <= n; i += stride) {
     float v[8];
-    LS8<DT>::load8(x, i, v);
+    VIO<DT>::load8(x, i, v);
 #pragma unroll
     for (int k = 0; k < 8; ++k) m = fmaxf(m, fabsf(v[k]));
   }
@@ -439,11 +284,119 @@ __global__ void amax_abs_kernel(const void* __restrict__ x, float* __restrict__ 
     atomicMax(reinterpret_cast<int*>(out), __float_as_int(m));  // m >= 0
 }
 
+// ---- host launchers -------------------------------------------------------
+static dim3 egrid(int64_t numel) {
+  return dim3((unsigned)elementwise_grid(cdiv((int)hmin<int64_t>(numel / 8 + 1, 1 << 30), 256)));
+}
+
+// bias_gelu: W = 16 elements per thread when d % 16 == 0, else 8
+static dim3 bias_gelu_grid(int64_t n, int64_t d) {
+  return egrid(d % 16 == 0 ? n * d / 2 : n * d);
+}
+
+template <bool FWD, bool BGRAD>
+static void bias_gelu_launch(dim3 g, const void* a, const void* x, const void* bias,
+                             void* out, int64_t n, int64_t d, float* ws, int dtype,
+                             hipStream_t s) {
+  by_dtype(dtype, [&](auto DT) {
+    by_flag(d % 16 == 0, [&](auto W16) {
+      hipLaunchKernelGGL((bias_gelu_kernel<DT(), FWD, W16() ? 16 : 8, BGRAD>), g,
+                         dim3(256), 0, s, a, x, bias, out, n, d, ws);
+    });
+  });
+}
+
+void bias_gelu_fwd(const void* x, const void* bias, void* y, int64_t n,
+                   int64_t d, int dtype, hipStream_t s) {
+  bias_gelu_launch<true, false>(bias_gelu_grid(n, d), x, x, bias, y, n, d, nullptr, dtype, s);
+}
+
+void bias_gelu_bwd(const void* dy, const void* x, const void* bias, void* dx,
+                   int64_t n, int64_t d, int dtype, hipStream_t s) {
+  bias_gelu_launch<false, false>(bias_gelu_grid(n, d), dy, x, bias, dx, n, d, nullptr, dtype, s);
+}
+
+// Grid of the backward with the bias gradient fused: the smallest multiple
+// of q = d / gcd(d, 256*W) blocks that covers the elementwise grid, within
+// the elementwise cap (else the largest multiple below the cap).  0: no such
+// grid, the caller runs bias_gelu_bwd followed by colsum.
+static int64_t gcd64(int64_t a, int64_t b) { while (b) { int64_t t = a % b; a = b; b = t; } return a; }
+
+int bias_gelu_bwd_db_grid(int64_t n, int64_t d) {
+  if (d % 8 != 0 || n <= 0) return 0;
+  const int W = d % 16 == 0 ? 16 : 8;
+  const int64_t cap = elementwise_grid(1LL << 40);
+  const int64_t g0 = bias_gelu_grid(n, d).x;
+  const int64_t q = d / gcd64(d, 256 * W);
+  if (q > cap) return 0;
+  int64_t g = (g0 + q - 1) / q * q;
+  if (g > cap) g = cap / q * q;
+  return (int)g;
+}
+
+void bias_gelu_bwd_db(const void* dy, const void* x, const void* bias, void* dx,
+                      float* db, float* ws, int grid, int64_t n, int64_t d,
+                      int dtype, hipStream_t s) {
+  const int W = d % 16 == 0 ? 16 : 8;
+  bias_gelu_launch<false, true>(dim3((unsigned)grid), dy, x, bias, dx, n, d, ws, dtype, s);
+  ws_reduce(ws, db, nullptr, (int)((int64_t)grid * 256 * W / d), 1, d, s);
+}
+
+void swiglu_fwd(const void* x, void* y, int64_t n, int64_t d, int dtype, hipStream_t s) {
+  by_dtype(dtype, [&](auto DT) {
+    hipLaunchKernelGGL((swiglu_fwd_kernel<DT()>), egrid(n * d), dim3(256), 0, s, x, y, n, d);
+  });
+}
+
+void swiglu_bwd(const void* dy, const void* x, void* dx, int64_t n, int64_t d,
+                int dtype, hipStream_t s) {
+  by_dtype(dtype, [&](auto DT) {
+    hipLaunchKernelGGL((swiglu_bwd_kernel<DT()>), egrid(n * d), dim3(256), 0, s, dy, x, dx, n, d);
+  });
+}
+
+void rope_fwd(const void* x, const float* cos_t, const float* sin_t, void* y,
+              int64_t b, int64_t sl, int64_t h, int64_t dh, int64_t pos_offset,
+              bool conj, int dtype, hipStream_t s) {
+  int64_t rows = b * sl * h;
+  dim3 g((unsigned)hmin<int64_t>(cdiv((int)hmin<int64_t>(rows, 1 << 24), 4), 2048));
+  float ssign = conj ? -1.f : 1.f;
+  by_dtype(dtype, [&](auto DT) {
+    hipLaunchKernelGGL((rope_kernel<DT()>), g, dim3(256), 0, s, x, cos_t, sin_t, y,
+                       b, sl, h, dh, pos_offset, ssign);
+  });
+}
+
+void colsum(const void* x, float* out, int64_t n, int64_t d, int dtype, hipStream_t s) {
+  dim3 grid((unsigned)cdiv((int)d, 256 * 8), col_chunks(n, d));
+  by_dtype(dtype, [&](auto DT) {
+    hipLaunchKernelGGL((colsum_kernel<DT()>), grid, dim3(256), 0, s, x, out, n, d);
+  });
+}
+
+void dropout_add_fwd(const void* x, const void* residual, void* y,
+                     uint8_t* mask, int64_t numel, float p, uint64_t seed,
+                     uint64_t offset, int dtype, hipStream_t s) {
+  by_dtype(dtype, [&](auto DT) {
+    hipLaunchKernelGGL((dropout_add_fwd_kernel<DT()>), egrid(numel), dim3(256), 0, s,
+                       x, residual, y, mask, numel, p, seed, offset);
+  });
+}
+
+void dropout_add_bwd(const void* dy, const uint8_t* mask, void* dx,
+                     int64_t numel, float p, int dtype, hipStream_t s) {
+  by_dtype(dtype, [&](auto DT) {
+    hipLaunchKernelGGL((dropout_add_bwd_kernel<DT()>), egrid(numel), dim3(256), 0, s,
+                       dy, mask, dx, numel, p);
+  });
+}
+
 void amax_abs(const void* x, float* out, int64_t n, int dtype, hipStream_t s) {
   int64_t waves = (n + 8 * 256 - 1) / (8 * 256);
   unsigned g = (unsigned)hmin<int64_t>(hmax<int64_t>(waves, 1), 4096);
-  EDT(dtype,
-      hipLaunchKernelGGL((amax_abs_kernel<kBF16>), dim3(g), dim3(256), 0, s, x, out, n),
-      hipLaunchKernelGGL((amax_abs_kernel<kF32>), dim3(g), dim3(256), 0, s, x, out, n));
+  by_dtype(dtype, [&](auto DT) {
+    hipLaunchKernelGGL((amax_abs_kernel<DT()>), dim3(g), dim3(256), 0, s, x, out, n);
+  });
 }
+
 }  // namespace pa

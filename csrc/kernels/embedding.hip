@@ -3,8 +3,7 @@
 // Reference behavior parity: paddle/phi/kernels/gpu/embedding_grad_kernel.cu
 // (EmbeddingGrad, atomic path).  fwd: one wave per token row; bwd: fp32
 // atomics into the dense grad table (device-scope atomicAdd, guide G12).
-#include "common.h"
-#include "api.h"
+#include "row_io.h"
 
 namespace pa {
 
@@ -64,24 +63,27 @@ __global__ void embedding_bwd_kernel(const void* __restrict__ dout,
   }
 }
 
+// one wave per id, 4 per block
+static dim3 embedding_grid(int64_t n_ids) {
+  return dim3((unsigned)hmin<int64_t>(cdiv((int)hmin<int64_t>(n_ids, 1 << 24), 4), 2048));
+}
+
 void embedding_fwd(const void* table, const int64_t* ids, void* out,
                    int64_t n_ids, int64_t d, int64_t vocab, int64_t padding_idx,
                    int dtype, hipStream_t s) {
-  dim3 g((unsigned)hmin<int64_t>(cdiv((int)hmin<int64_t>(n_ids, 1 << 24), 4), 2048));
-  if (dtype == kBF16)
-    hipLaunchKernelGGL((embedding_fwd_kernel<kBF16>), g, dim3(256), 0, s, table, ids, out, n_ids, d, vocab, padding_idx);
-  else
-    hipLaunchKernelGGL((embedding_fwd_kernel<kF32>), g, dim3(256), 0, s, table, ids, out, n_ids, d, vocab, padding_idx);
+  by_dtype(dtype, [&](auto DT) {
+    hipLaunchKernelGGL((embedding_fwd_kernel<DT()>), embedding_grid(n_ids), dim3(256), 0, s,
+                       table, ids, out, n_ids, d, vocab, padding_idx);
+  });
 }
 
 void embedding_bwd(const void* dout, const int64_t* ids, float* dtable,
                    int64_t n_ids, int64_t d, int64_t vocab, int64_t padding_idx,
                    int dtype, hipStream_t s) {
-  dim3 g((unsigned)hmin<int64_t>(cdiv((int)hmin<int64_t>(n_ids, 1 << 24), 4), 2048));
-  if (dtype == kBF16)
-    hipLaunchKernelGGL((embedding_bwd_kernel<kBF16>), g, dim3(256), 0, s, dout, ids, dtable, n_ids, d, vocab, padding_idx);
-  else
-    hipLaunchKernelGGL((embedding_bwd_kernel<kF32>), g, dim3(256), 0, s, dout, ids, dtable, n_ids, d, vocab, padding_idx);
+  by_dtype(dtype, [&](auto DT) {
+    hipLaunchKernelGGL((embedding_bwd_kernel<DT()>), embedding_grid(n_ids), dim3(256), 0, s,
+                       dout, ids, dtable, n_ids, d, vocab, padding_idx);
+  });
 }
 
 }  // namespace pa

@@ -14,55 +14,9 @@
 // re-derived, not ported.  LayerNorm's variance uses shifted single-pass
 // moments (see ln_fwd_kernel), not Welford merging; both are robust to a
 // row mean far from zero.
-#include "common.h"
-#include "api.h"
+#include "row_io.h"
 
 namespace pa {
-
-// -------- type abstraction: load/store 8 elems as fp32 ---------------------
-template <int DT> struct VIO;
-
-template <> struct VIO<kBF16> {
-  using ST = short;
-  static __device__ __forceinline__ void load8(const void* p, int64_t idx, float* f) {
-    shortx8 v = *reinterpret_cast<const shortx8*>((const short*)p + idx);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) f[i] = bf2f(v[i]);
-  }
-  static __device__ __forceinline__ void store8(void* p, int64_t idx, const float* f) {
-    shortx8 v;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) v[i] = f2bf(f[i]);
-    *reinterpret_cast<shortx8*>((short*)p + idx) = v;
-  }
-  static __device__ __forceinline__ float load1(const void* p, int64_t idx) {
-    return bf2f(((const short*)p)[idx]);
-  }
-  static __device__ __forceinline__ void store1(void* p, int64_t idx, float f) {
-    ((short*)p)[idx] = f2bf(f);
-  }
-};
-
-template <> struct VIO<kF32> {
-  using ST = float;
-  static __device__ __forceinline__ void load8(const void* p, int64_t idx, float* f) {
-    const float4* q = reinterpret_cast<const float4*>((const float*)p + idx);
-    float4 a = q[0], b = q[1];
-    f[0] = a.x; f[1] = a.y; f[2] = a.z; f[3] = a.w;
-    f[4] = b.x; f[5] = b.y; f[6] = b.z; f[7] = b.w;
-  }
-  static __device__ __forceinline__ void store8(void* p, int64_t idx, const float* f) {
-    float4* q = reinterpret_cast<float4*>((float*)p + idx);
-    q[0] = make_float4(f[0], f[1], f[2], f[3]);
-    q[1] = make_float4(f[4], f[5], f[6], f[7]);
-  }
-  static __device__ __forceinline__ float load1(const void* p, int64_t idx) {
-    return ((const float*)p)[idx];
-  }
-  static __device__ __forceinline__ void store1(void* p, int64_t idx, float f) {
-    ((float*)p)[idx] = f;
-  }
-};
 
 // ---------------------------------------------------------------------------
 // Pinned row arithmetic.  Each LayerNorm pass exists twice -- the generic
@@ -231,64 +185,52 @@ __global__ void ln_bwd_dx_kernel(const void* __restrict__ dy, const void* __rest
   }
 }
 
-// dw[d] = sum_n dy*xhat ; db[d] = sum_n dy.  Column-parallel: thread owns a
-// column, walks a row chunk, one atomicAdd per (column, chunk).
+// ---------------------------------------------------------------------------
+// Column reductions [n, d] -> fp32 [d] of the two-kernel backward: LayerNorm
+// dw/db (2 planes) and RMSNorm dw (1 plane).  A thread owns an 8-wide column
+// strip (16 B loads, d % 8 == 0) and walks the rows of its chunk (blockIdx.y)
+// in row order.  The chunk's sums go to ws[chunk][NOUT][d] with plain stores
+// and ws_reduce_kernel adds the chunks in a fixed order.  (One fp32 atomic
+// per (column, chunk) instead serializes ~chunks adds per column at one L2
+// bank: measured 3x over the HBM bound at n = 24k, d = 4k.)
+// ---------------------------------------------------------------------------
+// one element's terms: dy*xhat and dy | dy*x*rstd.  The products are
+// associated as written, fma(dy*rstd, x - mu, s0) and fma(x*rstd, dy, s0):
+// left to -ffast-math the association changes with the surrounding code.
+template <bool RMS>
+__device__ __forceinline__ void col_term(float g, float x, float mu, float rs,
+                                         float& s0, float& s1) {
+#pragma clang fp reassociate(off)
+  if (RMS) {
+    s0 = __builtin_fmaf(x * rs, g, s0);
+  } else {
+    s0 = __builtin_fmaf(g * rs, x - mu, s0);
+    s1 += g;
+  }
+}
+
 template <int DT, bool RMS>
-__global__ void ln_bwd_dwdb_kernel(const void* __restrict__ dy, const void* __restrict__ x,
+__global__ void col_partial_kernel(const void* __restrict__ dy, const void* __restrict__ x,
                                    const float* __restrict__ mean, const float* __restrict__ rstd,
-                                   float* __restrict__ dw, float* __restrict__ db,
-                                   int64_t n, int64_t d,
-                                   float* __restrict__ ws = nullptr) {
-  // 8-wide column strips (16 B loads) per thread; 2-D grid tiles rows;
-  // fp32 atomics once per (strip, row-chunk)
+                                   float* __restrict__ ws, int64_t n, int64_t d) {
+  constexpr int NOUT = RMS ? 1 : 2;
   int64_t c0 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 8;
   if (c0 >= d) return;
   int64_t rows_per = (n + gridDim.y - 1) / gridDim.y;
   int64_t r0 = (int64_t)blockIdx.y * rows_per;
   int64_t r1 = min(n, r0 + rows_per);
-  float aw[8] = {0.f}, ab[8] = {0.f};
-  if (c0 + 8 <= d) {
-    for (int64_t r = r0; r < r1; ++r) {
-      float g[8], xf[8];
-      VIO<DT>::load8(dy, r * d + c0, g);
-      VIO<DT>::load8(x, r * d + c0, xf);
-      float mu = RMS ? 0.f : mean[r], rs = rstd[r];
+  float s0[8] = {0.f}, s1[8] = {0.f};
+  for (int64_t r = r0; r < r1; ++r) {
+    float g[8], xf[8];
+    VIO<DT>::load8(dy, r * d + c0, g);
+    VIO<DT>::load8(x, r * d + c0, xf);
+    float mu = RMS ? 0.f : mean[r], rs = rstd[r];
 #pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        aw[k] += g[k] * (xf[k] - mu) * rs;
-        ab[k] += g[k];
-      }
-    }
-  } else {
-    for (int64_t r = r0; r < r1; ++r) {
-      float mu = RMS ? 0.f : mean[r], rs = rstd[r];
-      for (int64_t c = c0; c < d; ++c) {
-        float g = VIO<DT>::load1(dy, r * d + c);
-        float xf = VIO<DT>::load1(x, r * d + c);
-        aw[c - c0] += g * (xf - mu) * rs;
-        ab[c - c0] += g;
-      }
-    }
+    for (int k = 0; k < 8; ++k) col_term<RMS>(g[k], xf[k], mu, rs, s0[k], s1[k]);
   }
-  if (ws) {
-    // two-stage: plain partial stores, reduced by dwdb_reduce_kernel.
-    // The atomic path serializes ~chunks adds per column at one L2 bank
-    // (measured 3x over the HBM bound at n=24k, d=4k).
-    float* wrow = ws + (int64_t)(2 * blockIdx.y) * d;
-#pragma unroll
-    for (int k = 0; k < 8; ++k)
-      if (c0 + k < d) {
-        wrow[c0 + k] = aw[k];
-        wrow[d + c0 + k] = ab[k];
-      }
-    return;
-  }
-#pragma unroll
-  for (int k = 0; k < 8; ++k)
-    if (c0 + k < d) {
-      atomicAdd(&dw[c0 + k], aw[k]);
-      if (db) atomicAdd(&db[c0 + k], ab[k]);
-    }
+  float* wrow = ws + (int64_t)blockIdx.y * NOUT * d;
+  VIO<kF32>::store8(wrow, c0, s0);
+  if (NOUT == 2) VIO<kF32>::store8(wrow, d + c0, s1);
 }
 
 // ---------------------------------------------------------------------------
@@ -464,20 +406,6 @@ __global__ __launch_bounds__(1024) void ws_reduce_kernel(
   }
 }
 
-// reduce [2*chunks, d] partials -> dw[d], db[d]
-__global__ void dwdb_reduce_kernel(const float* __restrict__ ws, float* __restrict__ dw,
-                                   float* __restrict__ db, int chunks, int64_t d) {
-  int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= d) return;
-  float sw = 0.f, sb = 0.f;
-  for (int ch = 0; ch < chunks; ++ch) {
-    sw += ws[(int64_t)(2 * ch) * d + c];
-    sb += ws[(int64_t)(2 * ch) * d + d + c];
-  }
-  dw[c] = sw;
-  if (db) db[c] = sb;
-}
-
 // ---------------------------------------------------------------------------
 // RMSNorm (optionally fused residual-add: xr = x + residual; y = rms(xr)*w,
 // res_out = xr) -- matches fused_rms_norm semantics.
@@ -504,7 +432,7 @@ __global__ void rms_fwd_kernel(const void* __restrict__ x, const void* __restric
 #pragma unroll
       for (int k = 0; k < 8; ++k) sumsq += f[k] * f[k];
     }
-    if (HAS_RES) __syncthreads();  // res_out must be visible? (same thread re-reads its own slice only)
+    // no barrier for res_out: each thread reads back only what it stored itself
     float tss = block_reduce_256(sumsq, SumOp(), red, 0.f);
     float rstd = rsqrtf(tss / d + eps);
     if (threadIdx.x == 0) rstd_out[row] = rstd;
@@ -561,56 +489,35 @@ static int norm_grid(int64_t n) {
   return (int)(n < cap ? n : cap);
 }
 
-#define DT_SWITCH(dtype, ...)                         \
-  if (dtype == kBF16) {                               \
-    constexpr int DT = kBF16;                         \
-    __VA_ARGS__;                                      \
-  } else {                                            \
-    constexpr int DT = kF32;                          \
-    __VA_ARGS__;                                      \
+// strip count of the register-resident kernels, 1..4 for d <= 8192, as a
+// std::integral_constant
+template <class F>
+static void by_strips(int64_t d, F&& f) {
+  switch (cdiv((int)d, 2048)) {
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 3: f(std::integral_constant<int, 3>{}); break;
+    default: f(std::integral_constant<int, 4>{}); break;
   }
+}
 
 void layer_norm_fwd(const void* x, const void* w, const void* b, void* y,
                     float* mean, float* rstd, int64_t n, int64_t d, float eps,
                     int dtype, hipStream_t s) {
-  DT_SWITCH(dtype, hipLaunchKernelGGL((ln_fwd_kernel<DT>), dim3(norm_grid(n)),
-                                      dim3(256), 0, s, x, w, b, y, mean, rstd, n, d, eps));
+  by_dtype(dtype, [&](auto DT) {
+    hipLaunchKernelGGL((ln_fwd_kernel<DT()>), dim3(norm_grid(n)), dim3(256), 0, s,
+                       x, w, b, y, mean, rstd, n, d, eps);
+  });
 }
 
 void layer_norm_bwd_dx(const void* dy, const void* x, const void* w,
                        const float* mean, const float* rstd, void* dx,
                        int64_t n, int64_t d, int dtype, hipStream_t s) {
-  DT_SWITCH(dtype, hipLaunchKernelGGL((ln_bwd_dx_kernel<DT>), dim3(norm_grid(n)),
-                                      dim3(256), 0, s, dy, x, w, mean, rstd, dx, n, d));
+  by_dtype(dtype, [&](auto DT) {
+    hipLaunchKernelGGL((ln_bwd_dx_kernel<DT()>), dim3(norm_grid(n)), dim3(256), 0, s,
+                       dy, x, w, mean, rstd, dx, n, d);
+  });
 }
-
-int ln_dwdb_chunks(int64_t n, int64_t d) {
-  int xblocks = cdiv((int)d, 256 * 8);
-  return (int)hmin<int64_t>(hmax<int64_t>(1, n / 32),
-                            hmax<int64_t>(1, 2048 / xblocks));
-}
-
-void layer_norm_bwd_dwdb(const void* dy, const void* x, const float* mean,
-                         const float* rstd, float* dw, float* db, int64_t n,
-                         int64_t d, int dtype, hipStream_t s, float* ws) {
-  int xblocks = cdiv((int)d, 256 * 8);
-  int chunks = ln_dwdb_chunks(n, d);
-  dim3 grid((unsigned)xblocks, chunks);
-  DT_SWITCH(dtype, hipLaunchKernelGGL((ln_bwd_dwdb_kernel<DT, false>), grid,
-                                      dim3(256), 0, s, dy, x, mean, rstd, dw, db, n, d, ws));
-  if (ws)
-    hipLaunchKernelGGL(dwdb_reduce_kernel, dim3((unsigned)cdiv((int)d, 256)),
-                       dim3(256), 0, s, ws, dw, db, chunks, d);
-}
-
-// strip count of the register-resident kernels: 1..4 for d <= 8192
-#define NS_SWITCH(d, ...)                                            \
-  switch (cdiv((int)(d), 2048)) {                                    \
-    case 1: { constexpr int NS = 1; __VA_ARGS__; break; }            \
-    case 2: { constexpr int NS = 2; __VA_ARGS__; break; }            \
-    case 3: { constexpr int NS = 3; __VA_ARGS__; break; }            \
-    default: { constexpr int NS = 4; __VA_ARGS__; break; }           \
-  }
 
 bool ln_fused_ok(int64_t d) { return d % 8 == 0 && d <= kLnFusedMaxD; }
 
@@ -626,13 +533,50 @@ void ws_reduce(const float* ws, float* out0, float* out1, int parts, int nout,
                      parts, nout, d);
 }
 
+// row chunks of the column reductions (and of colsum): keep >= 1024
+// workgroups in flight (256 CUs / 8 XCDs want oversubscription), at least 32
+// rows per chunk
+int col_chunks(int64_t n, int64_t d) {
+  int xblocks = cdiv((int)d, 256 * 8);
+  return (int)hmin<int64_t>(hmax<int64_t>(1, n / 32),
+                            hmax<int64_t>(1, 2048 / xblocks));
+}
+
+template <bool RMS>
+static void col_reduce(const void* dy, const void* x, const float* mean,
+                       const float* rstd, float* dw, float* db, float* ws,
+                       int64_t n, int64_t d, int dtype, hipStream_t s) {
+  const int chunks = col_chunks(n, d);
+  dim3 grid((unsigned)cdiv((int)d, 256 * 8), chunks);
+  by_dtype(dtype, [&](auto DT) {
+    hipLaunchKernelGGL((col_partial_kernel<DT(), RMS>), grid, dim3(256), 0, s,
+                       dy, x, mean, rstd, ws, n, d);
+  });
+  ws_reduce(ws, dw, db, chunks, RMS ? 1 : 2, d, s);
+}
+
+void layer_norm_bwd_dwdb(const void* dy, const void* x, const float* mean,
+                         const float* rstd, float* dw, float* db, float* ws,
+                         int64_t n, int64_t d, int dtype, hipStream_t s) {
+  col_reduce<false>(dy, x, mean, rstd, dw, db, ws, n, d, dtype, s);
+}
+
+void rms_norm_bwd_dw(const void* dy, const void* x, const float* rstd,
+                     float* dw, float* ws, int64_t n, int64_t d, int dtype,
+                     hipStream_t s) {
+  col_reduce<true>(dy, x, nullptr, rstd, dw, nullptr, ws, n, d, dtype, s);
+}
+
 void add_layer_norm_fwd(const void* x, const void* residual, const void* w,
                         const void* b, void* h, void* y, float* mean,
                         float* rstd, int64_t n, int64_t d, float eps, int dtype,
                         hipStream_t s) {
-  DT_SWITCH(dtype, NS_SWITCH(d, hipLaunchKernelGGL(
-      (add_ln_fwd_kernel<DT, NS>), dim3(norm_grid(n)), dim3(256), 0, s, x,
-      residual, w, b, h, y, mean, rstd, n, d, eps)));
+  by_dtype(dtype, [&](auto DT) {
+    by_strips(d, [&](auto NS) {
+      hipLaunchKernelGGL((add_ln_fwd_kernel<DT(), NS()>), dim3(norm_grid(n)),
+                         dim3(256), 0, s, x, residual, w, b, h, y, mean, rstd, n, d, eps);
+    });
+  });
 }
 
 void layer_norm_bwd_fused(const void* dy, const void* x, const void* w,
@@ -640,48 +584,35 @@ void layer_norm_bwd_fused(const void* dy, const void* x, const void* w,
                           const void* dres, void* dx, float* dw, float* db,
                           float* ws, int grid, int64_t n, int64_t d, int dtype,
                           hipStream_t s) {
-  if (dres) {
-    DT_SWITCH(dtype, NS_SWITCH(d, hipLaunchKernelGGL(
-        (ln_bwd_fused_kernel<DT, NS, true>), dim3(grid), dim3(256), 0, s, dy, x,
-        w, mean, rstd, dres, dx, ws, n, d)));
-  } else {
-    DT_SWITCH(dtype, NS_SWITCH(d, hipLaunchKernelGGL(
-        (ln_bwd_fused_kernel<DT, NS, false>), dim3(grid), dim3(256), 0, s, dy, x,
-        w, mean, rstd, dres, dx, ws, n, d)));
-  }
+  by_dtype(dtype, [&](auto DT) {
+    by_strips(d, [&](auto NS) {
+      by_flag(dres != nullptr, [&](auto HAS_DRES) {
+        hipLaunchKernelGGL((ln_bwd_fused_kernel<DT(), NS(), HAS_DRES()>), dim3(grid),
+                           dim3(256), 0, s, dy, x, w, mean, rstd, dres, dx, ws, n, d);
+      });
+    });
+  });
   ws_reduce(ws, dw, db, grid, 2, d, s);
 }
 
 void rms_norm_fwd(const void* x, const void* residual, const void* w, void* y,
                   void* res_out, float* rstd, int64_t n, int64_t d, float eps,
                   int dtype, hipStream_t s) {
-  if (residual) {
-    DT_SWITCH(dtype, hipLaunchKernelGGL((rms_fwd_kernel<DT, true>), dim3(norm_grid(n)),
-                                        dim3(256), 0, s, x, residual, w, y, res_out, rstd, n, d, eps));
-  } else {
-    DT_SWITCH(dtype, hipLaunchKernelGGL((rms_fwd_kernel<DT, false>), dim3(norm_grid(n)),
-                                        dim3(256), 0, s, x, nullptr, w, y, nullptr, rstd, n, d, eps));
-  }
+  by_dtype(dtype, [&](auto DT) {
+    by_flag(residual != nullptr, [&](auto HAS_RES) {
+      hipLaunchKernelGGL((rms_fwd_kernel<DT(), HAS_RES()>), dim3(norm_grid(n)),
+                         dim3(256), 0, s, x, residual, w, y, res_out, rstd, n, d, eps);
+    });
+  });
 }
 
 void rms_norm_bwd_dx(const void* dy, const void* x, const void* w,
                      const float* rstd, void* dx, int64_t n, int64_t d,
                      int dtype, hipStream_t s) {
-  DT_SWITCH(dtype, hipLaunchKernelGGL((rms_bwd_dx_kernel<DT>), dim3(norm_grid(n)),
-                                      dim3(256), 0, s, dy, x, w, rstd, dx, n, d));
-}
-
-void rms_norm_bwd_dw(const void* dy, const void* x, const float* rstd,
-                     float* dw, int64_t n, int64_t d, int dtype, hipStream_t s,
-                     float* ws) {
-  int xblocks = cdiv((int)d, 256 * 8);
-  int chunks = ln_dwdb_chunks(n, d);
-  dim3 grid((unsigned)xblocks, chunks);
-  DT_SWITCH(dtype, hipLaunchKernelGGL((ln_bwd_dwdb_kernel<DT, true>), grid,
-                                      dim3(256), 0, s, dy, x, nullptr, rstd, dw, nullptr, n, d, ws));
-  if (ws)
-    hipLaunchKernelGGL(dwdb_reduce_kernel, dim3((unsigned)cdiv((int)d, 256)),
-                       dim3(256), 0, s, ws, dw, nullptr, chunks, d);
+  by_dtype(dtype, [&](auto DT) {
+    hipLaunchKernelGGL((rms_bwd_dx_kernel<DT()>), dim3(norm_grid(n)), dim3(256), 0, s,
+                       dy, x, w, rstd, dx, n, d);
+  });
 }
 
 }  // namespace pa

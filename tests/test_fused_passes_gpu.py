@@ -83,6 +83,7 @@ def test_layer_norm_bwd_one_pass(C, shape, dtype, has_bias, with_dres):
     compare(tag + " dw", dw, r64["dw"], atol=r64["A_dw"], dtype=F32)
     compare(tag + " db", db, r64["db"], atol=r64["A_db"], dtype=F32)
     compare(tag + " dw (two-kernel)", dw0, r64["dw"], atol=r64["A_dw"], dtype=F32)
+    compare(tag + " db (two-kernel)", db0, r64["db"], atol=r64["A_db"], dtype=F32)
 
 
 @pytest.mark.parametrize("dtype", [BF16, F32])

@@ -851,8 +851,13 @@ def test_embedding_all_ids_identical(dtype):
 # ---------------------------------------------------------------------------
 # colsum / l2_norm_squared / amax_abs
 # ---------------------------------------------------------------------------
+# one row chunk; the scalar path at d % 8 != 0; a partial last strip; 18
+# row chunks (the last one short); 64 row chunks (the last one empty)
+COLSUM_SHAPES = [(1, 13), (100, 13), (70, 4104), (600, 24), (2051, 64)]
+
+
 @pytest.mark.parametrize("dtype", [BF16, F32])
-@pytest.mark.parametrize("shape", [(1, 13), (100, 13), (70, 4104)])
+@pytest.mark.parametrize("shape", COLSUM_SHAPES)
 def test_colsum(shape, dtype):
     C = _ext.get_ext()
     x = randn(shape, 150, dtype)

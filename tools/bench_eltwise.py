@@ -48,6 +48,11 @@ report("bias_gelu bwd", t, 3 * M * F * 2 / GB)
 t = timeit(lambda: C.colsum(dy))
 report("colsum [16k,16k]", t, M * F * 2 / GB)
 
+# the L2-resident case _BiasGelu.backward sends to colsum (below 2^20 elements)
+small = torch.randn(256, 4096, device=DEV, dtype=torch.bfloat16)
+t = timeit(lambda: C.colsum(small), iters=200)
+report("colsum [256,4k]", t, 256 * 4096 * 2 / GB)
+
 x = torch.randn(M, H, device=DEV, dtype=torch.bfloat16)
 w = torch.randn(H, device=DEV, dtype=torch.bfloat16)
 bb = torch.randn(H, device=DEV, dtype=torch.bfloat16)
@@ -59,6 +64,10 @@ report("ln fwd [16k,4k]", t, 2 * M * H * 2 / GB)
 
 t = timeit(lambda: C.layer_norm_bwd(dyh, x, w, mean, rstd, True))
 report("ln bwd (dx+dwdb)", t, 5 * M * H * 2 / GB)
+
+_, rrstd = C.rms_norm_fwd(x, None, w, 1e-6)
+t = timeit(lambda: C.rms_norm_bwd(dyh, x, w, rrstd))
+report("rms_norm_bwd [16k,4k]", t, 5 * M * H * 2 / GB)
 
 r = torch.randn(M, H, device=DEV, dtype=torch.bfloat16)
 t = timeit(lambda: C.dropout_add_fwd(x, r, 0.1, 1234, 0))
