@@ -1054,6 +1054,58 @@ Tensor paged_prefill_attention(const Tensor& q, const Tensor& kcache,
   return o;
 }
 
+// ---- batched token sampling --------------------------------------------------
+// Contract of pa::SampleArgs (kernels/api.h, docs/KERNELS.md "token
+// sampling"); every check precedes the launch and the allocation.
+Tensor sample_tokens(const Tensor& logits, const Tensor& temperature,
+                     const Tensor& top_p, const Tensor& top_k,
+                     const Tensor& seed, const Tensor& offset,
+                     const c10::optional<Tensor>& rand_bits) {
+  const char* op = "sample_tokens";
+  TORCH_CHECK(logits.is_cuda(), op, ": logits must be a GPU tensor");
+  TORCH_CHECK(logits.scalar_type() == torch::kBFloat16 ||
+              logits.scalar_type() == torch::kFloat, op,
+              ": logits must be bfloat16 or float32, got ", logits.scalar_type());
+  TORCH_CHECK(logits.dim() == 2, op, ": logits must be [B, V], got rank ",
+              logits.dim());
+  const int64_t b = logits.size(0), v = logits.size(1);
+  TORCH_CHECK(b >= 1 && b < (1LL << 31), op, ": need 1 <= B < 2^31, got ", b);
+  TORCH_CHECK(v >= 1 && v < (1LL << 23), op, ": need 1 <= V < 2^23, got ", v);
+  TORCH_CHECK(logits.stride(1) == 1 || v == 1, op,
+              ": logits must have unit inner stride, got ", logits.stride(1));
+  TORCH_CHECK(logits.stride(0) >= 0, op, ": logits row stride is negative");
+  auto vec = [&](const Tensor& t, const char* name, torch::ScalarType st,
+                 const char* stname) {
+    TORCH_CHECK(t.is_cuda() && t.device() == logits.device(), op, ": ", name,
+                " must be on the GPU of logits");
+    TORCH_CHECK(t.scalar_type() == st && t.dim() == 1 && t.size(0) == b &&
+                t.is_contiguous(), op, ": ", name, " must be contiguous ",
+                stname, " [B]");
+  };
+  vec(temperature, "temperature", torch::kFloat, "float32");
+  vec(top_p, "top_p", torch::kFloat, "float32");
+  vec(top_k, "top_k", torch::kInt, "int32");
+  vec(seed, "seed", torch::kLong, "int64");
+  vec(offset, "offset", torch::kLong, "int64");
+  if (rand_bits.has_value()) vec(*rand_bits, "rand_bits", torch::kLong, "int64");
+  auto out = torch::empty({b}, logits.options().dtype(torch::kLong));
+  pa::SampleArgs a{};
+  a.logits = logits.const_data_ptr();
+  a.temperature = temperature.const_data_ptr<float>();
+  a.top_p = top_p.const_data_ptr<float>();
+  a.top_k = top_k.const_data_ptr<int>();
+  a.seed = seed.const_data_ptr<int64_t>();
+  a.offset = offset.const_data_ptr<int64_t>();
+  a.rand_bits = rand_bits.has_value() ? rand_bits->const_data_ptr<int64_t>()
+                                      : nullptr;
+  a.out = out.mutable_data_ptr<int64_t>();
+  a.b = (int)b; a.v = (int)v;
+  a.row_stride = logits.stride(0);
+  a.dtype = dt_of(logits);
+  pa::sample_tokens(a, cur_stream());
+  return out;
+}
+
 static bool aligned16(const Tensor& t) {
   return reinterpret_cast<uintptr_t>(t.const_data_ptr()) % 16 == 0;
 }
@@ -1532,6 +1584,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("seq_lens"), py::arg("cu_q"), py::arg("max_q"),
         py::arg("scale"), py::arg("k_scale") = c10::nullopt,
         py::arg("v_scale") = c10::nullopt);
+  m.def("sample_tokens", &sample_tokens, py::arg("logits"),
+        py::arg("temperature"), py::arg("top_p"), py::arg("top_k"),
+        py::arg("seed"), py::arg("offset"),
+        py::arg("rand_bits") = c10::nullopt);
   m.def("decode_attn_split_grid", &decode_attn_split_grid, py::arg("b"),
         py::arg("h"), py::arg("hkv"), py::arg("num_splits"), py::arg("int8"));
   m.def("mfma_probe", &mfma_probe);

@@ -21,6 +21,10 @@ TARGET = REPO / "paddle_amd" / "_C.so"
 ROCM = Path(os.environ.get("ROCM_PATH", "/opt/rocm"))
 HIPCC = str(ROCM / "bin" / "hipcc")
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")
+# per-source hipcc flags: new kernels are built without packed-fp32 VALU ops
+HIP_EXTRA = {
+    "sampling": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+}
 
 
 def _torch_paths():
@@ -65,7 +69,7 @@ def build(verbose: bool = False) -> Path:
         if _newer(src, obj, deps):
             cmd = [HIPCC, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC",
                    "-ffast-math", f"-I{CSRC}", "-c", str(src), "-o", str(obj)]
-            jobs.append(cmd)
+            jobs.append(cmd + HIP_EXTRA.get(src.stem, []))
 
     for cpp_name in ("bindings.cpp", "blaslt.cpp"):
         cpp_src = CSRC / cpp_name

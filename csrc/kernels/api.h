@@ -254,6 +254,44 @@ struct PrefillAttnArgs {
 };
 void paged_prefill_attention(const PrefillAttnArgs& a, hipStream_t s);
 
+// ---- batched token sampling (sampling.hip) ----------------------------------
+// out[b] = one token of row b of logits [b, v] (bf16 | fp32, unit inner
+// stride, row_stride in elements, rows need no alignment), 1 <= v < 2^23.
+// One launch, one block per row; no sort, no workspace, no host read.  The
+// result is exact: it does not depend on thread count or summation order.
+//   Order.   Tokens are ordered by (logit descending, index ascending); NaN
+//            orders lowest, -0 == +0.
+//   Greedy.  temperature <= 0 (or NaN), top_k == 1 or top_p <= 0: the first
+//            token in the order.  No random number is used.
+//   Weights. w_i = 2^40 for every element equal to the row maximum, else
+//            rint(2^40 * exp2((x_i - max) * (log2(e) / T))) in fp32 as u64
+//            (0 for a NaN); Z = sum w_i < 2^63.  All later sums are integer.
+//            A token with w_i = 0, probability under 2^-41 of the maximum's,
+//            cannot be drawn.
+//   Kept.    Token kept iff the weight strictly before it in the order is
+//            < ceil(fp64(top_p) * fp64(Z)) (top_p >= 1 keeps all) and, with
+//            top_k > 0, its rank is < top_k.  Equal logits are kept lowest
+//            index first.  The first token is always kept.
+//   Draw.    r = rand_bits[b] as u64 when rand_bits != null, else
+//            (x[0] << 32 | x[1]) of x = philox10(seed[b], offset[b]);
+//            t = mulhi64(r, Z_S), Z_S the kept weight; the result is the
+//            lowest kept index whose inclusive prefix sum of kept weights in
+//            INDEX order exceeds t.
+// Rows whose keys fit 128 KB (v <= 65536 bf16, 32768 fp32) stay in LDS after
+// one global read; longer rows re-read global memory on every pass.
+struct SampleArgs {
+  const void* logits;
+  const float *temperature, *top_p;
+  const int* top_k;                  // <= 0: off
+  const int64_t *seed, *offset;
+  const int64_t* rand_bits;          // null: Philox
+  int64_t* out;
+  int b, v;
+  long long row_stride;
+  int dtype;
+};
+void sample_tokens(const SampleArgs& a, hipStream_t s);
+
 // ---- dense MFMA GEMM (gemm.hip bf16, gemm_fp8.hip e4m3) --------------------
 // C[z] = op(A[z]) x op(B[z]) for z = 0 .. batch-1, fp32 accumulate, bf16 C.
 //   layout  kGemmNT: A[m][k], Bt[n][k]   kGemmNN: A[m][k], B[k][n]

@@ -1534,6 +1534,104 @@ def paged_prefill_attention(q, k_cache, v_cache, block_table, seq_lens, cu_q,
     return out
 
 
+# Batched token sampling (docs/KERNELS.md "token sampling").
+_M32 = 0xFFFFFFFF
+
+
+def _philox10(seed, ctr):
+    """Philox4x32-10 of csrc/common.h in Python integers: four 32-bit words
+    for the 64-bit (seed, counter)."""
+    seed &= (1 << 64) - 1
+    ctr &= (1 << 64) - 1
+    k0, k1 = seed & _M32, seed >> 32
+    c0, c1, c2, c3 = ctr & _M32, ctr >> 32, 0, 0
+    for _ in range(10):
+        p0, p1 = 0xD2511F53 * c0, 0xCD9E8D57 * c2
+        c0, c1, c2, c3 = (p1 >> 32) ^ c1 ^ k0, p1 & _M32, \
+            (p0 >> 32) ^ c3 ^ k1, p0 & _M32
+        k0, k1 = (k0 + 0x9E3779B9) & _M32, (k1 + 0xBB67AE85) & _M32
+    return c0, c1, c2, c3
+
+
+def _sample_keys(x):
+    """fp32 [B, V] -> int64 keys whose descending order is (logit descending),
+    NaN lowest and -0 == +0: the kernel's monotone keys."""
+    u = x.contiguous().view(torch.int32).long() & _M32
+    u = torch.where(u == 0x80000000, torch.zeros_like(u), u)
+    k = torch.where(u >= 0x80000000, ~u & _M32, u | 0x80000000)
+    return torch.where(torch.isnan(x), torch.zeros_like(k), k)
+
+
+def sample_tokens(logits, temperature, top_p, top_k, seed, offset,
+                  rand_bits=None):
+    """One token per row of logits [B, V] or [B, 1, V] (bf16 | fp32), int64
+    [B].  Per-row tensors of length B: temperature, top_p fp32; top_k int32
+    (<= 0 off); seed, offset int64; optional rand_bits int64, read as u64,
+    replaces the Philox draw of (seed, offset).
+    Tokens are ordered by (logit descending, index ascending), NaN lowest.
+    temperature <= 0, top_k == 1 or top_p <= 0 return the first token.  Else
+    w_i = 2^40 for the maxima and rint(2^40 * exp2((x_i - max) * log2(e) / T))
+    otherwise, all sums in integers; a token is kept iff the weight before it
+    in the order is < ceil(top_p * Z) and its rank is < top_k; with
+    t = (r * Z_S) >> 64 the result is the lowest kept index whose prefix sum
+    of kept weights in index order exceeds t.  On the GPU this is one launch
+    of the HIP kernel, which checks its own contract and reads nothing on the
+    host; the torch path below computes the same integers (up to the rounding
+    of exp2) and reads r on the host."""
+    if logits.dim() == 3 and logits.shape[1] == 1:
+        logits = logits[:, 0]
+    if _ext.use_native(logits):
+        return _ext.get_ext().sample_tokens(logits, temperature, top_p, top_k,
+                                            seed, offset, rand_bits)
+    if logits.dim() != 2 or logits.shape[0] < 1 or \
+            not 1 <= logits.shape[1] < 1 << 23:
+        raise ValueError("sample_tokens: logits must be [B, V] or [B, 1, V] "
+                         f"with B >= 1 and 1 <= V < 2^23, got {tuple(logits.shape)}")
+    B = logits.shape[0]
+    for name, t in (("temperature", temperature), ("top_p", top_p),
+                    ("top_k", top_k), ("seed", seed), ("offset", offset),
+                    ("rand_bits", rand_bits)):
+        if t is not None and tuple(t.shape) != (B,):
+            raise ValueError(f"sample_tokens: {name} must have shape [B]")
+    x = logits.float()
+    T, P, K = temperature.float(), top_p.float(), top_k.long()
+    greedy = ~(T > 0) | (K == 1) | ~(P > 0)
+    keys = _sample_keys(x)
+    _, order = torch.sort(keys, dim=1, descending=True, stable=True)
+    kmax = keys.gather(1, order[:, :1])
+    xmax = x.gather(1, order[:, :1])
+    c = torch.tensor(1.44269504088896, dtype=torch.float32, device=x.device) \
+        / torch.where(T > 0, T, torch.ones_like(T))
+    e = torch.exp2(torch.nan_to_num((x - xmax) * c[:, None], nan=-200.0,
+                                    posinf=0.0, neginf=-200.0))
+    w = torch.round(e * float(1 << 40)).long()
+    w = torch.where(keys == 0, torch.zeros_like(w), w)
+    w = torch.where(keys == kmax, torch.full_like(w, 1 << 40), w)
+    sw = w.gather(1, order)
+    before = sw.cumsum(1) - sw
+    # ceil(top_p * Z) in fp64, an integer below 2^63 where top_p < 1
+    thr = torch.ceil(torch.where(P < 1, P, torch.zeros_like(P)).double()
+                     * sw.sum(1).double()).long()
+    rank = torch.arange(x.shape[1], device=x.device)[None]
+    keep = ((P >= 1)[:, None] | (before < thr[:, None])) \
+        & ((K <= 0)[:, None] | (rank < K[:, None]))
+    keep[:, 0] = True
+    kw = torch.zeros_like(w).scatter(1, order, sw * keep)
+    cdf = kw.cumsum(1)
+    zs = cdf[:, -1].tolist()
+    if rand_bits is not None:
+        r = [int(v) & ((1 << 64) - 1) for v in rand_bits.tolist()]
+    else:
+        r = []
+        for s, o in zip(seed.tolist(), offset.tolist()):
+            x0, x1, _, _ = _philox10(int(s), int(o))
+            r.append(x0 << 32 | x1)
+    t = torch.tensor([(ri * z) >> 64 for ri, z in zip(r, zs)],
+                     dtype=torch.long, device=x.device)
+    drawn = torch.searchsorted(cdf, t[:, None], right=True)[:, 0]
+    return torch.where(greedy, order[:, 0], drawn)
+
+
 # ---------------------------------------------------------------------------
 # fused FFN: fc1(+bias+GELU in the hipBLASLt epilogue) -> fc2.
 # Backward folds dGELU + fc1 bias-grad into fc2's dgrad GEMM (DGELU_BGRAD),

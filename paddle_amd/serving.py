@@ -32,6 +32,10 @@ class Request:
     max_new_tokens: int = 32
     temperature: float = 0.0      # 0 => greedy
     top_p: float = 1.0
+    top_k: int = 0                # 0 => off
+    # Philox seed of a sampled request under sampling="device": token i is
+    # drawn from (seed, i).  None: Engine.add_request assigns the request id
+    seed: Optional[int] = None
     eos_token_id: Optional[int] = None
     # engine state
     rid: int = -1
@@ -84,6 +88,8 @@ class Engine:
     def add_request(self, req: Request):
         req.rid = self._next_rid
         self._next_rid += 1
+        if req.seed is None:
+            req.seed = req.rid
         req.enqueue_t = time.perf_counter()
         self.waiting.append(req)
         return req.rid
@@ -181,6 +187,8 @@ class GenerationServer:
             max_tokens: int = 32
             temperature: float = 0.0
             top_p: float = 1.0
+            top_k: int = 0
+            seed: Optional[int] = None
 
         api = FastAPI(title="paddle_amd serving")
 
@@ -188,7 +196,8 @@ class GenerationServer:
         def complete(body: CompletionIn):
             req = Request(prompt_ids=list(body.prompt),
                           max_new_tokens=body.max_tokens,
-                          temperature=body.temperature, top_p=body.top_p)
+                          temperature=body.temperature, top_p=body.top_p,
+                          top_k=body.top_k, seed=body.seed)
             self.engine.add_request(req)
             self.engine.run_until_done()
             return {"choices": [{"token_ids": req.out_ids}],
@@ -201,7 +210,8 @@ class GenerationServer:
 
             req = Request(prompt_ids=list(body.prompt),
                           max_new_tokens=body.max_tokens,
-                          temperature=body.temperature, top_p=body.top_p)
+                          temperature=body.temperature, top_p=body.top_p,
+                          top_k=body.top_k, seed=body.seed)
             self.engine.add_request(req)
 
             def gen():
@@ -240,7 +250,8 @@ class GPTModelRunner:
     def __init__(self, model, num_blocks=1024, block_size=16,
                  device=None, dtype=None, max_seq=2048, use_graphs=True,
                  weight_only=False, weight_only_group_size=-1,
-                 kv_cache="bf16", decode_splits=None, prefill_chunk=None):
+                 kv_cache="bf16", decode_splits=None, prefill_chunk=None,
+                 sampling="host"):
         import math
         from .ops import functional as hot
         self.hot = hot
@@ -257,6 +268,17 @@ class GPTModelRunner:
             raise ValueError("prefill_chunk must be None or an integer >= 1, "
                              f"got {prefill_chunk!r}")
         self.prefill_chunk = prefill_chunk
+        # sampling="host": sample_token per row (one sort and one sync each;
+        # greedy batches take one argmax).  "device": every pick is one
+        # sample_tokens launch over the batch and one sync; a request's token
+        # i is drawn from Philox(seed, i) whatever shares its batch, and
+        # sampled batches keep the steady-state graph path (docs/SERVING.md)
+        if sampling not in ("host", "device"):
+            raise ValueError("sampling must be 'host' or 'device', got "
+                             f"{sampling!r}")
+        self.sampling = sampling
+        self._gen = {}               # rid -> tokens picked so far (device)
+        self._samp = None            # (composition, per-slot parameters)
         self._prefilled = {}         # rid -> prompt tokens cached so far
         # decode_splits -> paged_decode_attention(num_splits=): None lets the
         # shape heuristic choose (bucket B and max_seq only, so each bucket's
@@ -337,6 +359,46 @@ class GPTModelRunner:
         return (layer.attn.qkv_proj(x)
                 .reshape(b, s, 3, self.H, self.D).unbind(2))
 
+    def _sample_params(self, reqs):
+        """Per-slot sample_tokens parameters of reqs on the device, built on
+        the host and shipped once; offset = tokens picked so far."""
+        def dev(x, dt):
+            return torch.tensor(x, dtype=dt).to(self.dev, non_blocking=True)
+        seeds = [(r.rid if r.seed is None else r.seed) & (2**64 - 1)
+                 for r in reqs]
+        return {"temperature": dev([r.temperature for r in reqs], torch.float32),
+                "top_p": dev([r.top_p for r in reqs], torch.float32),
+                "top_k": dev([r.top_k for r in reqs], torch.int32),
+                "seed": dev([s - 2**64 if s >= 2**63 else s for s in seeds],
+                            torch.int64),
+                "offset": dev([self._gen.get(r.rid, 0) for r in reqs],
+                              torch.int64)}
+
+    def _pick(self, logits, reqs, cache=False):
+        """sampling="device": tokens [len(reqs)] (device int64) for logits
+        [len(reqs), V] in one launch.  cache=True keeps the parameter tensors
+        while the composition stays and advances their offsets on the device."""
+        comp = tuple(r.rid for r in reqs)
+        if cache and self._samp is not None and self._samp[0] == comp:
+            p = self._samp[1]
+        else:
+            p = self._sample_params(reqs)
+            if cache:
+                self._samp = (comp, p)
+        picked = self.hot.sample_tokens(logits, p["temperature"], p["top_p"],
+                                        p["top_k"], p["seed"], p["offset"])
+        p["offset"] += 1
+        for r in reqs:
+            self._gen[r.rid] = self._gen.get(r.rid, 0) + 1
+        return picked
+
+    def _first_tokens(self, logits, reqs):
+        """First generated token of each request from its prefill logits."""
+        if self.sampling == "device":
+            return self._pick(logits, reqs).tolist()
+        return [sample_token(logits[i], r.temperature, r.top_p)
+                for i, r in enumerate(reqs)]
+
     @torch.no_grad()
     def _prefill(self, reqs, blocks):
         """Batched prefill for same-prompt-length requests (one flash-
@@ -360,10 +422,10 @@ class GPTModelRunner:
             x = x + layer.attn.out_proj(att.reshape(N, S0, -1))
             x = x + layer.mlp(layer.ln2(x))
         logits = m.lm_head(m.gpt.final_norm(x[:, -1]))
+        first = self._first_tokens(logits, reqs)
         for i, r in enumerate(reqs):
             self.seq_len[r.rid] = S0
-            self.last_token[r.rid] = sample_token(logits[i], r.temperature,
-                                                  r.top_p)
+            self.last_token[r.rid] = first[i]
 
     @torch.no_grad()
     def _prefill_chunked(self, reqs, blocks):
@@ -406,11 +468,11 @@ class GPTModelRunner:
         out = {}
         if fin:
             logits = self._chunk_logits(x[dev(last, torch.long)])
+            first = self._first_tokens(logits, fin)
             for i, r in enumerate(fin):
                 del self._prefilled[r.rid]
                 self.seq_len[r.rid] = len(r.prompt_ids)
-                self.last_token[r.rid] = sample_token(logits[i], r.temperature,
-                                                      r.top_p)
+                self.last_token[r.rid] = first[i]
                 out[r.rid] = self.last_token[r.rid]
         return out
 
@@ -458,10 +520,11 @@ class GPTModelRunner:
         Bp = B if not self.use_graphs else self._bucket(B)
         comp = tuple(r.rid for r in rest)
         all_greedy = all(r.temperature <= 0.0 for r in rest)
+        on_dev = self.sampling == "device"
         # steady-state fast path: same composition as last step, graph
-        # captured, greedy -- advance lens / rotate tokens entirely on
-        # device (zero H2D per step)
-        if (self.use_graphs and all_greedy and
+        # captured, greedy or device sampling -- advance lens / rotate
+        # tokens entirely on device (zero H2D per step)
+        if (self.use_graphs and (all_greedy or on_dev) and
                 comp == getattr(self, "_last_comp", None) and
                 Bp in self._graphs and
                 getattr(self, "_picked_dev", None) is not None):
@@ -474,7 +537,10 @@ class GPTModelRunner:
             st["wblk"][B:] = self.scratch_blk
             st["woff"].copy_((st["pos"] % self.bs).squeeze(1))
             g.replay()
-            self._picked_dev = st["logits"][:B].argmax(-1)
+            if on_dev:
+                self._picked_dev = self._pick(st["logits"][:B], rest, cache=True)
+            else:
+                self._picked_dev = st["logits"][:B].argmax(-1)
             picked = self._picked_dev.tolist()
             for i, r in enumerate(rest):
                 t = int(picked[i])
@@ -506,7 +572,12 @@ class GPTModelRunner:
         write_blk[B:] = self.scratch_blk
         logits = self._decode(Bp, toks, pos_ids, table, lens, write_blk,
                               write_off)
-        if all_greedy:
+        if on_dev:
+            # one sample_tokens launch + ONE device sync, greedy rows included
+            self._picked_dev = self._pick(logits[:B], rest, cache=True)
+            self._last_comp = comp
+            picked = self._picked_dev.tolist()
+        elif all_greedy:
             # greedy for the whole batch: ONE argmax + ONE device sync
             self._picked_dev = logits[:B].argmax(-1)
             self._last_comp = comp
@@ -683,10 +754,10 @@ class LlamaModelRunner(GPTModelRunner):
             x = x + layer.self_attn.o_proj(att.reshape(N, S0, -1))
             x = x + layer.mlp(layer.post_attention_layernorm(x))
         logits = m.lm_head(m.llama.norm(x[:, -1]))
+        first = self._first_tokens(logits, reqs)
         for i, r in enumerate(reqs):
             self.seq_len[r.rid] = S0
-            self.last_token[r.rid] = sample_token(logits[i], r.temperature,
-                                                  r.top_p)
+            self.last_token[r.rid] = first[i]
 
     def _chunk_forward(self, ids, pos, blk, off, table, lens, cu_q):
         m = self.model

@@ -20,7 +20,8 @@ from paddle_amd.serving import Engine, GPTModelRunner, Request  # noqa: E402
 def run_one(tag, model, n_req=64, prompt_len=128, gen_len=128, max_batch=32,
             num_blocks=4096, weight_only=False, runner_cls="gpt",
             group_size=-1, kv_cache="bf16", decode_splits=None,
-            prefill_chunk=None):
+            prefill_chunk=None, sampling="host", temperature=0.0, top_p=1.0,
+            top_k=0):
     cls = GPTModelRunner
     if runner_cls == "llama":
         from paddle_amd.serving import LlamaModelRunner
@@ -29,7 +30,7 @@ def run_one(tag, model, n_req=64, prompt_len=128, gen_len=128, max_batch=32,
                  max_seq=max(2048, prompt_len + gen_len),
                  weight_only=weight_only, weight_only_group_size=group_size,
                  kv_cache=kv_cache, decode_splits=decode_splits,
-                 prefill_chunk=prefill_chunk)
+                 prefill_chunk=prefill_chunk, sampling=sampling)
     pools = runner.k + runner.v + [s for s in runner.k_scale + runner.v_scale
                                    if s is not None]
     pool_gb = sum(t.numel() * t.element_size() for t in pools) / 2**30
@@ -42,7 +43,8 @@ def run_one(tag, model, n_req=64, prompt_len=128, gen_len=128, max_batch=32,
     for _ in range(n_req):
         eng.add_request(Request(
             prompt_ids=[random.randrange(V) for _ in range(prompt_len)],
-            max_new_tokens=gen_len))
+            max_new_tokens=gen_len, temperature=temperature, top_p=top_p,
+            top_k=top_k))
     t0 = time.perf_counter()
     # prefill wave (all same-length prompts); with --prefill-chunk only the
     # first chunk, and the steps counted below interleave prefill and decode
@@ -95,6 +97,14 @@ def main():
     ap.add_argument("--prefill-chunk", type=int, default=None,
                     help="runner prefill_chunk: unset = whole-prompt prefill, "
                          "n = at most n prompt tokens per engine step")
+    ap.add_argument("--temperature", type=float, default=0.0,
+                    help="request temperature (0 = greedy)")
+    ap.add_argument("--top-p", type=float, default=1.0)
+    ap.add_argument("--top-k", type=int, default=0,
+                    help="request top_k (0 = off; --sampling device only)")
+    ap.add_argument("--sampling", choices=["host", "device"], default="host",
+                    help="runner sampling: host = sample_token per row, "
+                         "device = one sample_tokens launch per step")
     args = ap.parse_args()
     paddle.seed(0)
     wo = args.weight_only_dtype or ("int8" if args.weight_only else False)
@@ -109,11 +119,16 @@ def main():
         tag_sfx += f" chunk={args.prefill_chunk}"
     if args.max_batch != 32:
         tag_sfx += f" b{args.max_batch}"
+    if args.sampling != "host" or args.temperature > 0:
+        tag_sfx += (f" sampling={args.sampling} T={args.temperature:g}"
+                    f" p={args.top_p:g} k={args.top_k}")
     kw = dict(weight_only=wo, group_size=args.group_size,
               kv_cache=args.kv_cache, prompt_len=args.prompt_len,
               gen_len=args.gen_len, n_req=args.n_req,
               max_batch=args.max_batch, decode_splits=args.decode_splits,
-              prefill_chunk=args.prefill_chunk)
+              prefill_chunk=args.prefill_chunk, sampling=args.sampling,
+              temperature=args.temperature, top_p=args.top_p,
+              top_k=args.top_k)
     seq = max(2048, args.prompt_len + args.gen_len)
     # blocks for max_batch sequences of prompt+gen tokens, with headroom
     nblk = max(8192, 2 * 32 * (-(-seq // 16)))
