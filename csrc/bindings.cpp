@@ -286,6 +286,40 @@ Tensor colsum(const Tensor& x) {
   return out;
 }
 
+// {x^T} or {x^T, fp32 column sums of x}: x bf16 [r, c] with unit inner stride
+// (a column slice of a wider tensor is fine), the result contiguous [c, r].
+std::vector<Tensor> transpose_colsum(const Tensor& x, bool want_sums) {
+  const char* op = "transpose_colsum";
+  TORCH_CHECK(x.is_cuda(), op, ": x must be a GPU tensor");
+  TORCH_CHECK(x.scalar_type() == torch::kBFloat16, op, ": x must be bfloat16, got ",
+              x.scalar_type());
+  TORCH_CHECK(x.dim() == 2, op, ": x must have rank 2, got ", x.dim());
+  const int64_t r = x.size(0), c = x.size(1), lim = (int64_t)1 << 31;
+  TORCH_CHECK(r >= 1 && c >= 1 && r < lim && c < lim, op,
+              ": x must have 1 <= rows, columns < 2^31, got [", r, ", ", c, "]");
+  TORCH_CHECK(r % 8 == 0, op, ": x rows must be a multiple of 8, got ", r);
+  TORCH_CHECK(c % 8 == 0, op, ": x columns must be a multiple of 8, got ", c);
+  TORCH_CHECK(x.stride(1) == 1, op, ": x must have unit inner stride, got ",
+              x.stride(1));
+  TORCH_CHECK(x.stride(0) % 8 == 0 && x.stride(0) >= 0 &&
+                  reinterpret_cast<uintptr_t>(x.const_data_ptr()) % 16 == 0,
+              op, ": x rows must start on 16-byte boundaries (row stride ",
+              x.stride(0), ", storage offset ", x.storage_offset(), ")");
+  auto out = torch::empty({c, r}, x.options());
+  Tensor sums, ws;
+  if (want_sums) {
+    const auto f32 = x.options().dtype(torch::kFloat);
+    sums = torch::empty({c}, f32);
+    ws = torch::empty({(int64_t)pa::transpose_plan(r, c).chunks * c}, f32);
+  }
+  pa::transpose_colsum(x.const_data_ptr(), out.mutable_data_ptr(),
+                       want_sums ? sums.mutable_data_ptr<float>() : nullptr,
+                       want_sums ? ws.mutable_data_ptr<float>() : nullptr, r, c,
+                       x.stride(0), cur_stream());
+  if (want_sums) return {out, sums};
+  return {out};
+}
+
 // {dx, db}: db fp32 [d] = column sum of dx as stored.  One kernel plus a
 // partials reduce when a grid keeps each thread on its columns (fused =
 // true and bias_gelu_bwd_db_grid > 0), else bias_gelu_bwd then colsum.
@@ -1510,6 +1544,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("swiglu_bwd", &swiglu_bwd);
   m.def("rope_fwd", &rope_fwd);
   m.def("colsum", &colsum);
+  m.def("transpose_colsum", &transpose_colsum, py::arg("x"),
+        py::arg("want_sums") = false);
   m.def("adamw", &adamw);
   m.def("fc1_gelu_fwd", &pa_lt::fc1_gelu_fwd);
   m.def("fc2_dgrad_dgelu", &pa_lt::fc2_dgrad_dgelu);

@@ -22,8 +22,10 @@ ROCM = Path(os.environ.get("ROCM_PATH", "/opt/rocm"))
 HIPCC = str(ROCM / "bin" / "hipcc")
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")
 # per-source hipcc flags: new kernels are built without packed-fp32 VALU ops
+_NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 HIP_EXTRA = {
-    "sampling": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+    "sampling": _NO_PK_F32,
+    "transpose": _NO_PK_F32,
 }
 
 

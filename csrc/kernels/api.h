@@ -106,6 +106,18 @@ void amax_abs(const void* x, float* out, int64_t n, int dtype, hipStream_t s);
 void colsum(const void* x, float* out, int64_t n, int64_t d, int dtype,
             hipStream_t s);
 
+// ---- transpose with column sums (transpose.hip) -----------------------------
+// out [c, r] contiguous = x [r, c]^T, bf16, x with unit inner stride and row
+// stride ld in elements.  sums non-null: sums[c] = fp32 column sums of x, from
+// per-chunk partials ws [transpose_plan(r, c).chunks][c] added in a fixed
+// order (ws and sums need no initialisation, no atomics).
+// Contract (checked by the binding): r % 8 == 0, c % 8 == 0, ld % 8 == 0,
+// 1 <= r, c < 2^31, x and out 16-byte aligned.
+struct TransposePlan { int tiles_per_chunk, chunks; };
+TransposePlan transpose_plan(int64_t r, int64_t c);
+void transpose_colsum(const void* x, void* out, float* sums, float* ws,
+                      int64_t r, int64_t c, int64_t ld, hipStream_t s);
+
 // ---- fused AdamW (flat shards; fp32 master + bf16 model params) -----------
 void adamw(float* master, void* param_bf16, const void* grad, float* m,
            float* v, int64_t numel, float lr, float beta1, float beta2,

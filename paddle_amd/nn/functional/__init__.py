@@ -47,6 +47,11 @@ def linear(x, weight, bias=None, name=None):
         out = C.decode_gemm_mfma(x.reshape(-1, k).contiguous(), weight,
                                  hot._as_dtype(bias, x.dtype))
         return out.reshape(*x.shape[:-1], n)
+    # Training at the sizes where the weight gradient pays for transposed,
+    # K-contiguous operands: the same library calls, with the backward's dw
+    # and db made by hot._wgrad.
+    if hot._lt_linear_ok(x, weight, bias):
+        return hot.linear_lt(x, weight, bias)
     if bias is not None and x.dim() >= 2:
         x2 = x.reshape(-1, x.shape[-1])
         out = torch.addmm(bias, x2, weight)

@@ -1658,10 +1658,11 @@ class _FusedFFN(torch.autograd.Function):
         x2, w1, w2, z, g = ctx.saved_tensors
         dy2 = dy.reshape(-1, dy.shape[-1]).contiguous()
         dz1, db1 = C.fc2_dgrad_dgelu(dy2, w2, z)   # dGELU + bias-grad fused
-        dw2 = g.t() @ dy2
-        db2 = dy2.sum(0)
+        dw2, db2 = _wgrad(g, dy2, want_db=True)
+        if db2 is None:
+            db2 = dy2.sum(0)
         dx = dz1 @ w1.t()
-        dw1 = x2.t() @ dz1
+        dw1 = _wgrad(x2, dz1)
         return dx.reshape(ctx.xshape), dw1, db1, dw2, db2
 
 
@@ -1687,11 +1688,121 @@ def _own_dgrad_ok(dy2, w):
         and _gd.own_gemm_ok(dy2, w, "nt")
 
 
-def _wgrad(x2, dy2):
-    if _gd.use_own("tn", x2.shape[1], dy2.shape[1], x2.shape[0]) \
+# Wgrad forms, dw[in, out] from x2 [T, in] and dy2 [T, out]
+# (docs/KERNELS.md "Wgrad in a K-contiguous layout"):
+#   "tn"      x2.t() @ dy2: both operands strided along the contraction T
+#   "xt"      xt @ dy2 with xt = x2^T contiguous [in, T]
+#   "xt_dyt"  xt @ dyt.t(), both T-contiguous; the kernel that transposes dy2
+#             yields its column sums, the bias gradient, on the way
+# The transposes cost two passes over the operand and pay for themselves only
+# where the GEMM is long: the gate is the region tools/bench_gemm.py
+# --wgrad-layout measured (profiles/wgrad_layout.txt).
+#
+# Measured at T = 16384 and 24576 on (in, out) = (4096, 12288), (4096, 4096),
+# (4096, 16384) and (16384, 4096).  Transposing dy costs T*out and buys ~9 %
+# of a GEMM of T*in*out: it paid at in 16384 > out, and at in 4096 only where
+# its column sums replace a bias reduction; on fc1 (in 4096, out 16384, no
+# bias) "xt" won.  Hence: dy is transposed when in > out or db is wanted.
+# The LM head (out 50304, a 2.5 GB dlogits transpose) is not measured.
+_WGRAD_KC_MIN_T = 16384
+_WGRAD_KC_DIMS = (4096, 16384)    # min and max of in and out
+
+
+def _wgrad_kc_size(t, n_in, n_out):
+    lo, hi = _WGRAD_KC_DIMS
+    return (t >= _WGRAD_KC_MIN_T and min(n_in, n_out) >= lo
+            and max(n_in, n_out) <= hi)
+
+
+def _wgrad_form(x2, dy2, want_db=False):
+    """The form _wgrad runs when the caller names none."""
+    n_in, n_out = x2.shape[1], dy2.shape[1]
+    if not (_wgrad_kc_size(x2.shape[0], n_in, n_out) and not _tracing()
+            and _gd._native_ok(x2) and _gd.transpose_ok(x2)):
+        return "tn"
+    if (want_db or n_in > n_out) and _gd.transpose_ok(dy2):
+        return "xt_dyt"
+    return "xt"
+
+
+def _wgrad(x2, dy2, want_db=False, form=None):
+    """dw, or (dw, db) with want_db: db is colsum(dy2) in dy2's dtype where
+    the form makes it on the way, else None and the caller reduces dy2.
+    xt / dyt live only inside this call."""
+    form = form or _wgrad_form(x2, dy2, want_db)
+    db = None
+    if form == "xt":
+        dw = torch.matmul(_gd.transpose_colsum(x2), dy2)
+    elif form == "xt_dyt":
+        if want_db:
+            dyt, db = _gd.transpose_colsum(dy2, True)
+            db = db.to(dy2.dtype)
+        else:
+            dyt = _gd.transpose_colsum(dy2)
+        dw = torch.matmul(_gd.transpose_colsum(x2), dyt.t())
+    elif _gd.use_own("tn", x2.shape[1], dy2.shape[1], x2.shape[0]) \
             and _gd.own_gemm_ok(x2, dy2, "tn"):
-        return _gd.gemm_tn(x2, dy2)
-    return torch.matmul(x2.t(), dy2)
+        dw = _gd.gemm_tn(x2, dy2)
+    else:
+        dw = torch.matmul(x2.t(), dy2)
+    return (dw, db) if want_db else dw
+
+
+class _LinearLt(torch.autograd.Function):
+    """y = x @ W (+ bias) by hipBLASLt, the very calls nn.functional.linear
+    makes outside this Function; the backward takes dw, and db where it comes
+    for free, from _wgrad's K-contiguous forms instead of autograd's
+    x.t() @ dy and dy.sum(0)."""
+
+    @staticmethod
+    def forward(ctx, x, w, bias, form):
+        if bias is not None:
+            y = torch.addmm(bias, x.reshape(-1, x.shape[-1]), w)
+            y = y.reshape(*x.shape[:-1], w.shape[-1])
+        else:
+            y = torch.matmul(x, w)
+        ctx.save_for_backward(x, w)
+        ctx.has_bias, ctx.form = bias is not None, form
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w = ctx.saved_tensors
+        dy2 = dy.reshape(-1, dy.shape[-1])
+        dx = dw = db = None
+        if ctx.needs_input_grad[0]:
+            dx = torch.matmul(dy2, w.t()).reshape(x.shape)
+        want_db = ctx.has_bias and ctx.needs_input_grad[2]
+        if ctx.needs_input_grad[1]:
+            x2 = x.reshape(-1, x.shape[-1])
+            if want_db:
+                dw, db = _wgrad(x2, dy2, want_db=True, form=ctx.form)
+            else:
+                dw = _wgrad(x2, dy2, form=ctx.form)
+        if want_db and db is None:
+            db = dy2.sum(0)
+        return dx, dw, db, None
+
+
+def _lt_linear_ok(x, w, bias):
+    """True when nn.functional.linear's library path runs through _LinearLt.
+    False leaves its old calls to run literally: CPU, fp32, auto_cast mixes,
+    inference, tracing, sizes below the measured gate, an x off the transpose
+    contract.  dy's strides are known only in the backward, where
+    _wgrad_form looks again."""
+    if not (torch.is_grad_enabled() and not torch.is_autocast_enabled()
+            and x.is_cuda and x.dim() >= 2 and w.dim() == 2 and w.requires_grad
+            and x.dtype == w.dtype == torch.bfloat16 and x.is_contiguous()
+            and (bias is None or (bias.dtype == torch.bfloat16 and bias.dim() == 1))):
+        return False
+    x2 = x.reshape(-1, x.shape[-1])
+    return (_wgrad_kc_size(x2.shape[0], w.shape[0], w.shape[1])
+            and w.shape[1] % 8 == 0 and not _tracing()
+            and _gd._native_ok(x2) and _gd.transpose_ok(x2))
+
+
+def linear_lt(x, w, bias=None, form=None):
+    return _LinearLt.apply(x, w, bias, form)
 
 
 def _colsum(dy2, dtype):

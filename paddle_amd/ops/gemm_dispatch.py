@@ -82,6 +82,23 @@ def own_gemm_ok(a: torch.Tensor, b: torch.Tensor, layout: str) -> bool:
     return k == kb and k >= 64 and a.numel() > 0 and b.numel() > 0
 
 
+def transpose_ok(x) -> bool:
+    """True when x meets transpose_colsum's contract (csrc/kernels/api.h): a
+    GPU bf16 matrix with unit inner stride, rows and columns multiples of 8
+    and below 2^31, every row starting on a 16-byte boundary.  Pure, like
+    own_gemm_ok: callers keep the strided-operand wgrad when it is False."""
+    return (isinstance(x, torch.Tensor) and x.is_cuda and _operand_ok(x)
+            and 0 < x.shape[0] < 2 ** 31 and 0 < x.shape[1] < 2 ** 31
+            and x.shape[0] % 8 == 0 and x.shape[1] % 8 == 0)
+
+
+def transpose_colsum(x: torch.Tensor, want_sums: bool = False):
+    """x^T contiguous, or (x^T, fp32 column sums of x) with want_sums."""
+    C = _ext.get_ext()
+    outs = C.transpose_colsum(x, want_sums)
+    return tuple(outs) if want_sums else outs[0]
+
+
 def _native_ok(x: torch.Tensor) -> bool:
     return x.is_cuda and x.dtype == torch.bfloat16 and _ext.use_native(x)
 

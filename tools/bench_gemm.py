@@ -6,6 +6,10 @@
 and writes paddle_amd/ops/gemm_table.json -- the committed dispatch
 table (reference pattern: matmul_kernel_impl.h:914-958).
 
+--wgrad-layout: times the flagship weight gradients by operand layout
+(strided, x transposed, x and dy transposed) with the transposes each
+needs, and writes the raw lines to profiles/wgrad_layout.txt (--out).
+
 Layout conventions (paddle Linear W [K, N]):
   nt fwd:   C[M,N] = X[M,K] @ Wt[N,K]^T      (Wt = cached transpose)
   nt dgrad: dX[M,K] = dY[M,N] @ W[K,N]^T'    (W is already NT's B-operand)
@@ -67,7 +71,16 @@ def main():
     ap.add_argument("--autotune", action="store_true")
     ap.add_argument("--fp8", action="store_true")
     ap.add_argument("--iters", type=int, default=10)
+    ap.add_argument("--wgrad-layout", action="store_true",
+                    help="wgrad by operand layout at the flagship shapes")
+    ap.add_argument("--tokens", type=int, nargs="+", default=[24576])
+    ap.add_argument("--out", default=os.path.join(
+        os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
+        "profiles", "wgrad_layout.txt"))
     args = ap.parse_args()
+    if args.wgrad_layout:
+        wgrad_layout(args.iters, args.tokens, args.out)
+        return
     if args.autotune:
         autotune(args.iters)
         return
@@ -192,6 +205,88 @@ def autotune(iters):
     os.makedirs("gpurun_out", exist_ok=True)
     with open(out, "w") as f:
         json.dump({"version": 1, "entries": entries}, f, indent=1)
+
+
+def _times_ms(fn, iters, warmup=3):
+    """Per-call device times by events, ms."""
+    for _ in range(warmup):
+        fn()
+    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+          for _ in range(iters)]
+    torch.cuda.synchronize()
+    for a, b in ev:
+        a.record()
+        fn()
+        b.record()
+    torch.cuda.synchronize()
+    return [a.elapsed_time(b) for a, b in ev]
+
+
+def wgrad_layout(iters, tokens, out_path, rounds=2):
+    """Wgrad dw[in, out] = x[T, in]^T dy[T, out] by operand layout:
+      a  x.t() @ dy            both strided along T (today)
+      b  xt @ dy               xt = x^T contiguous
+      c  xt @ dyt.t()          both T-contiguous
+    plus what each form needs or saves: the transposes (torch copy and the
+    transpose_colsum kernel, with and without sums) and dy.sum(0).  Every
+    entry is timed in `rounds` alternating rounds; net per round is
+    GEMM + own transposes (- the bias reduction for c with a bias)."""
+    from paddle_amd import _ext
+    C = _ext.get_ext()
+    lines = []
+
+    def emit(s):
+        print(s, flush=True)
+        lines.append(s)
+
+    emit(f"# {torch.cuda.get_device_name(0)}  iters {iters}  rounds {rounds}  "
+         f"ms as mean/min per round")
+    for t in tokens:
+        for name, _, k, n in SHAPES_B12[:4]:
+            x = torch.randn(t, k, device="cuda", dtype=torch.bfloat16)
+            dy = torch.randn(t, n, device="cuda", dtype=torch.bfloat16)
+            xt = x.t().contiguous()
+            dyt = dy.t().contiguous()
+            assert torch.equal(C.transpose_colsum(x, False)[0], xt)
+            assert torch.equal(C.transpose_colsum(dy, True)[0], dyt)
+            ref = torch.matmul(x.t(), dy).float()
+            for tag, got in (("b", torch.matmul(xt, dy)), ("c", torch.matmul(xt, dyt.t()))):
+                _check(got, ref, f"{name} {tag}")
+            del ref, got
+            cases = [
+                ("a", lambda: torch.matmul(x.t(), dy)),
+                ("b", lambda: torch.matmul(xt, dy)),
+                ("c", lambda: torch.matmul(xt, dyt.t())),
+                ("x_t_torch", lambda: x.t().contiguous()),
+                ("dy_t_torch", lambda: dy.t().contiguous()),
+                ("x_t_own", lambda: C.transpose_colsum(x, False)),
+                ("dy_t_own", lambda: C.transpose_colsum(dy, False)),
+                ("dy_t_own_sums", lambda: C.transpose_colsum(dy, True)),
+                ("dy_sum0", lambda: dy.sum(0)),
+            ]
+            flops = 2.0 * t * k * n
+            res = {c[0]: [] for c in cases}
+            for _ in range(rounds):
+                for tag, fn in cases:
+                    ms = _times_ms(fn, iters)
+                    res[tag].append((sum(ms) / len(ms), min(ms)))
+            for tag, _ in cases:
+                rr = "  ".join(f"{m:8.4f}/{lo:8.4f}" for m, lo in res[tag])
+                tf = f"  {flops / res[tag][0][0] / 1e9:7.1f} TF" if tag in "abc" else ""
+                emit(f"{name:5s} T{t} in{k} out{n} {tag:14s} {rr}{tf}")
+            for r in range(rounds):
+                a_min = res["a"][r][1]
+                net_b = res["b"][r][0] + res["x_t_own"][r][0]
+                net_c = res["c"][r][0] + res["x_t_own"][r][0] + res["dy_t_own"][r][0]
+                net_cb = (res["c"][r][0] + res["x_t_own"][r][0]
+                          + res["dy_t_own_sums"][r][0] - res["dy_sum0"][r][0])
+                emit(f"{name:5s} T{t} round {r}: a min {a_min:.4f}  net b {net_b:.4f}  "
+                     f"net c {net_c:.4f}  net c with bias {net_cb:.4f}")
+            del x, dy, xt, dyt
+            torch.cuda.empty_cache()
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "w") as f:
+        f.write("\n".join(lines) + "\n")
 
 
 def bench_fp8():
