@@ -1473,6 +1473,176 @@ std::vector<Tensor> moe_assign_slots(const Tensor& topi, int64_t num_experts,
   return {slot, counts};
 }
 
+// ---- MoE dispatch / combine ---------------------------------------------------
+// Contract of pa::moe_route and pa::MoePermuteArgs (kernels/api.h,
+// docs/KERNELS.md "MoE dispatch / combine"); every check precedes the launch
+// and the allocation.
+static void moe_check_map(const char* op, const char* name, const Tensor& m,
+                          int64_t dim) {
+  TORCH_CHECK(m.is_cuda(), op, ": ", name, " must be a GPU tensor");
+  TORCH_CHECK(m.scalar_type() == torch::kInt32 && m.dim() == dim &&
+              m.is_contiguous(), op, ": ", name, " must be contiguous int32 "
+              "with ", dim, " dimension(s)");
+}
+
+static void moe_check_tk(const char* op, const char* name, const Tensor& m) {
+  TORCH_CHECK(m.size(1) >= 1 && m.size(1) <= 8, op, ": ", name,
+              " needs 1 <= K <= 8, got K = ", m.size(1));
+  TORCH_CHECK(m.size(0) * m.size(1) < (1LL << 31), op, ": ", name,
+              " needs T * K < 2^31, got T = ", m.size(0));
+}
+
+static void moe_check_rows(const char* op, const char* name, const Tensor& x) {
+  TORCH_CHECK(x.is_cuda(), op, ": ", name, " must be a GPU tensor");
+  TORCH_CHECK(x.scalar_type() == torch::kBFloat16 ||
+              x.scalar_type() == torch::kFloat, op, ": ", name,
+              " must be bfloat16 or float32, got ", x.scalar_type());
+  TORCH_CHECK(x.dim() == 2 && x.is_contiguous(), op, ": ", name,
+              " must be contiguous [rows, h]");
+  TORCH_CHECK(x.size(1) >= 8 && x.size(1) % 8 == 0 && x.size(1) < (1LL << 31),
+              op, ": ", name, " needs h % 8 == 0 and 8 <= h < 2^31, got h = ",
+              x.size(1));
+  TORCH_CHECK(aligned16(x), op, ": ", name, " must be 16-byte aligned");
+}
+
+// operand next to the rows `x`: same GPU; rows also share dtype and h
+static void moe_check_with(const char* op, const char* name, const Tensor& t,
+                           const Tensor& x, bool rows) {
+  TORCH_CHECK(t.device() == x.device(), op, ": ", name,
+              " must be on the GPU of the rows");
+  if (rows)
+    TORCH_CHECK(t.scalar_type() == x.scalar_type() && t.size(1) == x.size(1),
+                op, ": ", name, " must have the dtype and h of the rows");
+}
+
+static void moe_check_w(const char* op, const char* name, const Tensor& w,
+                        int64_t t, int64_t k) {
+  TORCH_CHECK(w.is_cuda(), op, ": ", name, " must be a GPU tensor");
+  TORCH_CHECK(w.scalar_type() == torch::kFloat && w.dim() == 2 &&
+              w.size(0) == t && w.size(1) == k && w.is_contiguous(), op, ": ",
+              name, " must be contiguous float32 [T, K] = [", t, ", ", k, "]");
+}
+
+static int64_t moe_check_slots(const char* op, const Tensor& src_of) {
+  const int64_t s = src_of.size(0);
+  TORCH_CHECK(s >= 1 && s < (1LL << 31), op,
+              ": src_of needs 1 <= E * cap < 2^31 entries, got ", s);
+  return s;
+}
+
+std::vector<Tensor> moe_route(const Tensor& topi, int64_t num_experts,
+                              int64_t cap, int64_t block_waves) {
+  const char* op = "moe_route";
+  moe_check_map(op, "topi", topi, 2);
+  moe_check_tk(op, "topi", topi);
+  TORCH_CHECK(num_experts >= 1, op, ": num_experts must be >= 1, got ",
+              num_experts);
+  TORCH_CHECK(cap >= 1, op, ": cap must be >= 1, got ", cap);
+  TORCH_CHECK(num_experts < (1LL << 31) && cap < (1LL << 31) &&
+              num_experts * cap < (1LL << 31), op,
+              ": num_experts * cap must be < 2^31");
+  TORCH_CHECK(block_waves == 0 || block_waves == 1 || block_waves == 4 ||
+              block_waves == 16, op, ": block_waves must be 0, 1, 4 or 16");
+  const int64_t t = topi.size(0), k = topi.size(1);
+  if (t == 0)
+    return {torch::empty({0, k}, topi.options()),
+            torch::full({num_experts * cap}, -1, topi.options()),
+            torch::zeros({num_experts}, topi.options())};
+  auto slot_of = torch::empty({t, k}, topi.options());
+  auto src_of = torch::empty({num_experts * cap}, topi.options());
+  auto counts = torch::empty({num_experts}, topi.options());
+  pa::moe_route(topi.const_data_ptr<int>(), slot_of.mutable_data_ptr<int>(),
+                src_of.mutable_data_ptr<int>(), counts.mutable_data_ptr<int>(),
+                t, num_experts, k, cap, (int)block_waves, cur_stream());
+  return {slot_of, src_of, counts};
+}
+
+// x [T, h] -> [E * cap, h]; k: the K of the route that made src_of
+Tensor moe_dispatch(const Tensor& x, const Tensor& src_of, int64_t k) {
+  const char* op = "moe_dispatch";
+  moe_check_rows(op, "x", x);
+  moe_check_map(op, "src_of", src_of, 1);
+  moe_check_with(op, "src_of", src_of, x, false);
+  const int64_t slots = moe_check_slots(op, src_of);
+  TORCH_CHECK(k >= 1 && k <= 8, op, ": needs 1 <= K <= 8, got K = ", k);
+  TORCH_CHECK(x.size(0) * k < (1LL << 31), op, ": x needs T * K < 2^31, got T = ",
+              x.size(0));
+  if (x.size(0) == 0) return torch::zeros({slots, x.size(1)}, x.options());
+  auto out = torch::empty({slots, x.size(1)}, x.options());
+  pa::MoePermuteArgs a{};
+  a.x = x.const_data_ptr();
+  a.src_of = src_of.const_data_ptr<int>();
+  a.out = out.mutable_data_ptr();
+  a.t = (int)x.size(0); a.k = (int)k; a.slots = (int)slots;
+  a.h = (int)x.size(1); a.dtype = dt_of(x);
+  pa::moe_dispatch(a, cur_stream());
+  return out;
+}
+
+// y [E * cap, h] -> [T, h]; w null: unweighted
+Tensor moe_combine(const Tensor& y, const c10::optional<Tensor>& w,
+                   const Tensor& slot_of) {
+  const char* op = "moe_combine";
+  moe_check_rows(op, "y", y);
+  moe_check_map(op, "slot_of", slot_of, 2);
+  moe_check_with(op, "slot_of", slot_of, y, false);
+  const int64_t t = slot_of.size(0), k = slot_of.size(1);
+  moe_check_tk(op, "slot_of", slot_of);
+  TORCH_CHECK(y.size(0) < (1LL << 31), op,
+              ": y needs E * cap < 2^31 rows, got ", y.size(0));
+  if (w.has_value()) {
+    moe_check_w(op, "w", *w, t, k);
+    moe_check_with(op, "w", *w, y, false);
+  }
+  auto out = torch::empty({t, y.size(1)}, y.options());
+  if (t == 0) return out;
+  pa::MoePermuteArgs a{};
+  a.x = y.const_data_ptr();
+  a.w = w.has_value() ? w->const_data_ptr<float>() : nullptr;
+  a.slot_of = slot_of.const_data_ptr<int>();
+  a.out = out.mutable_data_ptr();
+  a.t = (int)t; a.k = (int)k; a.slots = (int)y.size(0);
+  a.h = (int)y.size(1); a.dtype = dt_of(y);
+  pa::moe_combine(a, cur_stream());
+  return out;
+}
+
+// -> dy [E * cap, h] and dw fp32 [T, K] (0 for dropped entries)
+std::vector<Tensor> moe_combine_bwd(const Tensor& y, const Tensor& dout,
+                                    const Tensor& w, const Tensor& src_of) {
+  const char* op = "moe_combine_bwd";
+  moe_check_rows(op, "y", y);
+  moe_check_map(op, "src_of", src_of, 1);
+  moe_check_with(op, "src_of", src_of, y, false);
+  const int64_t slots = moe_check_slots(op, src_of);
+  TORCH_CHECK(y.size(0) == slots, op, ": y must have one row per src_of entry, "
+              "got ", y.size(0), " rows for ", slots, " slots");
+  TORCH_CHECK(w.dim() == 2, op, ": w must be contiguous float32 [T, K]");
+  const int64_t t = w.size(0), k = w.size(1);
+  moe_check_w(op, "w", w, t, k);
+  moe_check_with(op, "w", w, y, false);
+  moe_check_tk(op, "w", w);
+  moe_check_rows(op, "dout", dout);
+  moe_check_with(op, "dout", dout, y, true);
+  TORCH_CHECK(dout.size(0) == t, op, ": dout must have T = ", t, " rows, got ",
+              dout.size(0));
+  if (t == 0)
+    return {torch::zeros_like(y), torch::zeros({0, k}, w.options())};
+  auto dy = torch::empty_like(y);
+  auto dw = torch::zeros({t, k}, w.options());
+  pa::MoePermuteArgs a{};
+  a.x = y.const_data_ptr();
+  a.dout = dout.const_data_ptr();
+  a.w = w.const_data_ptr<float>();
+  a.src_of = src_of.const_data_ptr<int>();
+  a.out = dy.mutable_data_ptr();
+  a.dw = dw.mutable_data_ptr<float>();
+  a.t = (int)t; a.k = (int)k; a.slots = (int)slots;
+  a.h = (int)y.size(1); a.dtype = dt_of(y);
+  pa::moe_combine_bwd(a, cur_stream());
+  return {dy, dw};
+}
+
 Tensor amax_abs(const Tensor& x) {
   CHECK_IN(x);
   auto out = torch::zeros({}, x.options().dtype(torch::kFloat));
@@ -1568,6 +1738,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("group_size"), py::arg("out_dtype"));
   m.def("moe_gate_topk", &moe_gate_topk);
   m.def("moe_assign_slots", &moe_assign_slots);
+  m.def("moe_route", &moe_route, py::arg("topi"), py::arg("num_experts"),
+        py::arg("cap"), py::arg("block_waves") = 0);
+  m.def("moe_dispatch", &moe_dispatch, py::arg("x"), py::arg("src_of"),
+        py::arg("k"));
+  m.def("moe_combine", &moe_combine, py::arg("y"), py::arg("w"),
+        py::arg("slot_of"));
+  m.def("moe_combine_bwd", &moe_combine_bwd);
   m.def("gemm_fp8_nt", &gemm_fp8_nt, py::arg("a"), py::arg("bt"),
         py::arg("scale_ab") = 1.0, py::arg("bias") = c10::nullopt);
   m.def("gemm_fp8_nt_batched", &gemm_fp8_nt_batched, py::arg("a"),

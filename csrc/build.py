@@ -26,6 +26,7 @@ _NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 HIP_EXTRA = {
     "sampling": _NO_PK_F32,
     "transpose": _NO_PK_F32,
+    "moe_permute": _NO_PK_F32,
 }
 
 

@@ -380,4 +380,49 @@ void moe_gate_topk(const float* logits, float* topv, int* topi, float* me,
 void moe_assign_slots(const int* topi, int* slot_of, int* counts, int64_t t,
                       int64_t e, int64_t k, int64_t cap, hipStream_t s);
 
+// ---- MoE dispatch / combine over collision-free slot maps -------------------
+// moe_route (moe.hip): topi int32 [T, K] -> slot_of [T, K], src_of [E * cap],
+// counts [E], all int32 and all written in full by the kernel.  In GShard
+// order, pos(t, kk) = #{(t', kk') : topi[t', kk'] == topi[t, kk] and
+// (kk', t') < (kk, t)}; slot_of[t, kk] = e * cap + pos if pos < cap else -1;
+// src_of[e * cap + pos] = t * K + kk, -1 on the empty tail; counts[e] counts
+// dropped entries too.  An id outside [0, E) gets slot -1 and is not counted.
+// block_waves: waves per expert block, 1 | 4 | 16, 0 = by problem size.
+void moe_route(const int* topi, int* slot_of, int* src_of, int* counts,
+               int64_t t, int64_t e, int64_t k, int64_t cap, int block_waves,
+               hipStream_t s);
+// Row movers (moe_permute.hip).  slots = E * cap.
+//   moe_dispatch:    out[s] = x[src_of[s] / K], zeros for an empty slot; x
+//                    [T, h], out [slots, h]; a bit copy.
+//   moe_combine:     out[t] = sum_kk w[t, kk] * x[slot_of[t, kk]] over kept kk,
+//                    fp32 accumulation, one rounding; x [slots, h], out [T, h];
+//                    w null = weight 1 (the backward of dispatch).
+//   moe_combine_bwd: out[s] = w[src] * dout[t] and dw[src] = <x[s], dout[t]>
+//                    in fp32 for src = src_of[s] kept, t = src / K; else
+//                    out[s] = 0.  x = y [slots, h], dout [T, h], out = dy
+//                    [slots, h]; dw [T, K] comes in zeroed.
+// Contract (checked by the binding before any launch or allocation,
+// docs/KERNELS.md "MoE dispatch / combine"):
+//   * all tensors on one GPU;
+//   * rows (x, dout, out) bf16 or fp32, one dtype per call, contiguous
+//     [., h], 16-byte aligned, h % 8 == 0;
+//   * maps int32 and contiguous, slot_of [T, K], src_of [slots];
+//   * w and dw fp32 contiguous [T, K];
+//   * 1 <= K <= 8, E >= 1, cap >= 1, T * K < 2^31, E * cap < 2^31;
+//   * T == 0 returns empty or zero outputs without a launch.
+// A src_of entry outside [0, T * K) counts as empty and a slot_of entry
+// outside [0, slots) as dropped; neither is used as an index.
+struct MoePermuteArgs {
+  const void* x;
+  const void* dout;
+  const float* w;
+  const int *slot_of, *src_of;
+  void* out;
+  float* dw;
+  int t, k, slots, h, dtype;
+};
+void moe_dispatch(const MoePermuteArgs& a, hipStream_t s);
+void moe_combine(const MoePermuteArgs& a, hipStream_t s);
+void moe_combine_bwd(const MoePermuteArgs& a, hipStream_t s);
+
 }  // namespace pa

@@ -1,5 +1,6 @@
 // MoE routing kernels for gfx950: fused top-k gate + deterministic
-// capacity slot assignment.
+// capacity slot assignment, and the collision-free slot maps of the fused
+// dispatch / combine path (moe_route, row movers in moe_permute.hip).
 //
 // Reference role: paddle/phi/kernels/gpu/{assign_pos,number_count,
 // limit_by_capacity,prune_gate_by_capacity}_kernel.cu + the gate math in
@@ -10,8 +11,12 @@
 //   * assign: one wave per (expert, k) walks tokens in 64-chunks using
 //     __ballot + popc prefix -- positions follow token order exactly like
 //     the reference's cumsum (deterministic capacity dropping), no sort
+//   * route: one block per expert owns the whole (kk, t) sequence of its
+//     expert, so positions run on across kk (GShard order: every first
+//     choice before every second choice) and no two (t, kk) share a slot
 #include "common.h"
 #include "api.h"
+#include <type_traits>
 
 namespace pa {
 
@@ -71,6 +76,65 @@ __global__ void moe_assign_kernel(const int* __restrict__ topi,
   if (lane == 0) atomicAdd(&counts[e], base);
 }
 
+// topi [T, K] i32 -> slot_of [T, K], src_of [E * cap], counts [E], every
+// element written here by plain stores (no initialisation, no atomics).
+// Block e walks the sequence i = kk * T + t in 64-chunks; pos(t, kk) is the
+// number of earlier entries of the sequence that chose e.  NW == 1 is one
+// wave carrying `base` through the walk.  NW > 1 cuts the chunk list into NW
+// consecutive runs: every wave counts its run, the counts meet in LDS once,
+// and each wave walks its run again from the sum of the runs before it.
+// Block 0 also writes -1 for expert ids outside [0, E).
+template <int NW>
+__global__ __launch_bounds__(NW * 64) void moe_route_kernel(
+    const int* __restrict__ topi, int* __restrict__ slot_of,
+    int* __restrict__ src_of, int* __restrict__ counts, int T, int E, int K,
+    int cap) {
+  __shared__ int wcount[NW];
+  const int e = blockIdx.x;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int nch = (T + 63) >> 6;           // 64-chunks per kk
+  const int total = nch * K;
+  const int per = (total + NW - 1) / NW;
+  const int c0 = min(total, wv * per), c1 = min(total, c0 + per);
+  const unsigned long long below = (1ull << lane) - 1;
+  int base = 0, n_e = 0;
+  if (NW > 1) {
+    int n = 0;
+    for (int c = c0; c < c1; ++c) {
+      const int kk = c / nch, t = ((c - kk * nch) << 6) + lane;
+      n += __popcll(__ballot(t < T && topi[t * K + kk] == e));
+    }
+    if (lane == 0) wcount[wv] = n;
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < NW; ++i) {
+      if (i < wv) base += wcount[i];
+      n_e += wcount[i];
+    }
+  }
+  for (int c = c0; c < c1; ++c) {
+    const int kk = c / nch, t = ((c - kk * nch) << 6) + lane;
+    const int id = (t < T) ? topi[t * K + kk] : e + 1;
+    const bool match = (t < T) && id == e;
+    const unsigned long long mask = __ballot(match);
+    if (match) {
+      const int pos = base + __popcll(mask & below);
+      if (pos < cap) {
+        slot_of[t * K + kk] = e * cap + pos;
+        src_of[e * cap + pos] = t * K + kk;
+      } else {
+        slot_of[t * K + kk] = -1;
+      }
+    }
+    if (e == 0 && t < T && (unsigned)id >= (unsigned)E) slot_of[t * K + kk] = -1;
+    base += __popcll(mask);
+  }
+  if (NW == 1) n_e = base;
+  for (int p = min(n_e, cap) + (int)threadIdx.x; p < cap; p += NW * 64)
+    src_of[e * cap + p] = -1;
+  if (threadIdx.x == 0) counts[e] = n_e;
+}
+
 void moe_gate_topk(const float* logits, float* topv, int* topi, float* me,
                    float* ce, int64_t t, int64_t e, int64_t k, hipStream_t s) {
   long long waves = t;
@@ -85,6 +149,25 @@ void moe_assign_slots(const int* topi, int* slot_of, int* counts, int64_t t,
   dim3 g((unsigned)((waves * 64 + 255) / 256));
   hipLaunchKernelGGL(moe_assign_kernel, g, dim3(256), 0, s, topi, slot_of,
                      counts, t, (int)e, (int)k, (int)cap);
+}
+
+// block_waves: 1, 4 or 16 waves per expert block; 0 picks by the length of
+// the walk (measured at T = 8192, docs/KERNELS.md "MoE dispatch / combine")
+void moe_route(const int* topi, int* slot_of, int* src_of, int* counts,
+               int64_t t, int64_t e, int64_t k, int64_t cap, int block_waves,
+               hipStream_t s) {
+  if (block_waves == 0) {
+    const int64_t chunks = ((t + 63) / 64) * k;
+    block_waves = chunks <= 4 ? 1 : chunks <= 64 ? 4 : 16;
+  }
+  auto go = [&](auto NW) {
+    hipLaunchKernelGGL((moe_route_kernel<NW()>), dim3((unsigned)e),
+                       dim3(NW() * 64), 0, s, topi, slot_of, src_of, counts,
+                       (int)t, (int)e, (int)k, (int)cap);
+  };
+  if (block_waves == 1) go(std::integral_constant<int, 1>{});
+  else if (block_waves == 4) go(std::integral_constant<int, 4>{});
+  else go(std::integral_constant<int, 16>{});
 }
 
 }  // namespace pa

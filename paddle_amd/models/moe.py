@@ -178,11 +178,23 @@ class _GroupedFFN(torch.autograd.Function):
 
 
 class MoELayer(nn.Layer):
-    """Token dispatch -> EP all-to-all -> local experts -> combine."""
+    """Token dispatch -> EP all-to-all -> local experts -> combine.
+
+    dispatch="index" (default): torch index ops per k around slots counted
+    per (expert, k).  dispatch="fused": moe_route / moe_dispatch / moe_combine
+    (ops/functional.py) -- slots unique across k in GShard order, fp32 gate
+    weights, one rounding in the combine, no Python loop over k and no host
+    read.  The two modes drop different tokens at k >= 2, so their results
+    differ."""
 
     def __init__(self, hidden_size, inter_size, num_experts, k=2,
-                 capacity_factor=2.0, ep_group=None, grouped=True):
+                 capacity_factor=2.0, ep_group=None, grouped=True,
+                 dispatch="index"):
         super().__init__()
+        if dispatch not in ("index", "fused"):
+            raise ValueError(f"MoELayer: dispatch must be 'index' or 'fused', "
+                             f"got {dispatch!r}")
+        self.dispatch = dispatch
         self.ep_group = ep_group
         self.ep_size = ep_group.nranks if ep_group else 1
         assert num_experts % self.ep_size == 0
@@ -207,6 +219,11 @@ class MoELayer(nn.Layer):
         self.aux_loss = aux
         cap = int(self.capacity_factor * T * self.k / self.num_experts) + 1
         cap = max(cap, 4)
+        if self.dispatch == "fused":
+            slot_of, src_of, _ = hot.moe_route(topi, self.num_experts, cap)
+            back = self._experts(hot.moe_dispatch(tokens, src_of, slot_of), cap, h)
+            out = hot.moe_combine(back, topv.float(), slot_of, src_of)
+            return out.view(b, s, h)
 
         # build per-expert capacity-padded dispatch buffer [E, cap, h]
         dispatch = torch.zeros(self.num_experts, cap, h, dtype=x.dtype, device=x.device)
@@ -243,6 +260,17 @@ class MoELayer(nn.Layer):
             combine_w[:, kk] = torch.where(valid, topv[:, kk].to(x.dtype),
                                            torch.zeros_like(combine_w[:, kk]))
 
+        back = self._experts(dispatch, cap, h)
+
+        out = torch.zeros_like(tokens)
+        for kk in range(self.k):
+            valid = slot_of[:, kk] >= 0
+            idx = slot_of[valid, kk]
+            out[valid] += back[idx] * combine_w[valid, kk].unsqueeze(-1)
+        return out.view(b, s, h)
+
+    def _experts(self, dispatch, cap, h):
+        """[E * cap, h] slot rows -> all-to-all -> experts -> all-to-all."""
         # EP all-to-all: [E, cap, h] -> experts-local [ep, local_E, cap, h]
         dd = _AllToAll.apply(dispatch.reshape(self.ep_size, self.local_experts, cap, h)
                              .contiguous().view(-1, h), self.ep_group)
@@ -261,24 +289,18 @@ class MoELayer(nn.Layer):
             expert_out = torch.stack(outs, dim=1)  # [ep, local_E, cap, h]
 
         back = _AllToAll.apply(expert_out.contiguous().view(-1, h), self.ep_group)
-        back = back.view(self.num_experts * cap, h)
-
-        out = torch.zeros_like(tokens)
-        for kk in range(self.k):
-            valid = slot_of[:, kk] >= 0
-            idx = slot_of[valid, kk]
-            out[valid] += back[idx] * combine_w[valid, kk].unsqueeze(-1)
-        return out.view(b, s, h)
+        return back.view(self.num_experts * cap, h)
 
 
 class MoEDecoderLayer(nn.Layer):
-    def __init__(self, cfg: GPTConfig, num_experts, k=2, ep_group=None):
+    def __init__(self, cfg: GPTConfig, num_experts, k=2, ep_group=None,
+                 moe_dispatch="index"):
         super().__init__()
         self.ln1 = nn.LayerNorm(cfg.hidden_size)
         self.attn = GPTAttention(cfg)
         self.ln2 = nn.LayerNorm(cfg.hidden_size)
         self.moe = MoELayer(cfg.hidden_size, cfg.intermediate_size, num_experts,
-                            k=k, ep_group=ep_group)
+                            k=k, ep_group=ep_group, dispatch=moe_dispatch)
 
     def forward(self, x):
         h = x + self.attn(self.ln1(x))
@@ -287,12 +309,13 @@ class MoEDecoderLayer(nn.Layer):
 
 class GPTMoEForPretraining(nn.Layer):
     def __init__(self, cfg: GPTConfig, num_experts=64, k=2, ep_group=None,
-                 aux_weight=0.01):
+                 aux_weight=0.01, moe_dispatch="index"):
         super().__init__()
         self.cfg = cfg
         self.aux_weight = aux_weight
         self.embeddings = GPTEmbeddings(cfg)
-        self.layers = nn.LayerList([MoEDecoderLayer(cfg, num_experts, k, ep_group)
+        self.layers = nn.LayerList([MoEDecoderLayer(cfg, num_experts, k, ep_group,
+                                                    moe_dispatch)
                                     for _ in range(cfg.num_layers)])
         self.final_norm = nn.LayerNorm(cfg.hidden_size)
         self.lm_head = nn.Linear(cfg.hidden_size, cfg.vocab_size, bias_attr=False)

@@ -1633,6 +1633,122 @@ def sample_tokens(logits, temperature, top_p, top_k, seed, offset,
 
 
 # ---------------------------------------------------------------------------
+# MoE dispatch / combine over collision-free slot maps (csrc/kernels/moe.hip
+# moe_route, moe_permute.hip; docs/KERNELS.md "MoE dispatch / combine").
+# Reference role: incubate/distributed/models/moe MoEScatter / MoEGather.
+# The torch paths below are the executable spec: same semantics, no
+# boolean-mask indexing, so no host read either.
+# ---------------------------------------------------------------------------
+def _moe_native_ok(rows, *others):
+    """Row kernels: bf16 | fp32 contiguous [., h], h % 8 == 0, every operand
+    on the rows' GPU.  The bindings check the rest and raise."""
+    return (_ext.use_native(rows) and rows.dtype in _NATIVE_DTYPES
+            and rows.dim() == 2 and rows.shape[1] % 8 == 0
+            and rows.shape[1] >= 8
+            and all(o.device == rows.device for o in others))
+
+
+def moe_route(topi, num_experts, cap):
+    """topi integer [T, K] -> (slot_of [T, K], src_of [E * cap], counts [E]),
+    int32.  GShard order: entry (t, kk) takes position pos = the number of
+    entries (t', kk') with the same expert and (kk', t') < (kk, t), so all
+    first choices come before all second choices and no two entries share a
+    slot.  slot_of = e * cap + pos, or -1 when pos >= cap; src_of[slot] =
+    t * K + kk, -1 for an empty slot; counts[e] counts dropped entries too.
+    An expert id outside [0, E) gets slot -1 and is counted nowhere."""
+    E, cap = int(num_experts), int(cap)
+    if _ext.use_native(topi):
+        return tuple(_ext.get_ext().moe_route(
+            topi.to(torch.int32).contiguous(), E, cap))
+    if topi.dim() != 2 or not 1 <= topi.shape[1] <= 8 or E < 1 or cap < 1:
+        raise ValueError("moe_route: topi must be [T, K] with 1 <= K <= 8, "
+                         "num_experts >= 1 and cap >= 1")
+    T, K = topi.shape
+    dev = topi.device
+    ids = topi.t().reshape(-1).long()                  # sequence i = kk * T + t
+    ok = (ids >= 0) & (ids < E)
+    key = torch.where(ok, ids, torch.full_like(ids, E))
+    counts = torch.zeros(E + 1, dtype=torch.long, device=dev).scatter_add_(
+        0, key, torch.ones_like(key))
+    order = torch.argsort(key, stable=True)
+    start = counts.cumsum(0) - counts
+    pos = torch.empty_like(key)
+    pos[order] = torch.arange(K * T, device=dev) - start[key[order]]
+    kept = ok & (pos < cap)
+    slot = torch.where(kept, ids * cap + pos, torch.full_like(ids, -1))
+    i = torch.arange(K * T, device=dev)
+    src = (i % max(T, 1)) * K + i // max(T, 1)
+    src_of = torch.full((E * cap + 1,), -1, dtype=torch.long, device=dev)
+    src_of.scatter_(0, torch.where(kept, slot, torch.full_like(slot, E * cap)),
+                    torch.where(kept, src, torch.full_like(src, -1)))
+    return (slot.view(K, T).t().contiguous().to(torch.int32),
+            src_of[:-1].to(torch.int32), counts[:E].to(torch.int32))
+
+
+def _moe_gather_rows(rows, idx, valid):
+    """rows[idx] where valid else zeros; idx is clamped, never a mask index."""
+    if rows.shape[0] == 0:
+        return rows.new_zeros(*idx.shape, rows.shape[1])
+    got = rows[idx.clamp(0, rows.shape[0] - 1).long()]
+    return torch.where(valid.unsqueeze(-1), got, torch.zeros_like(got))
+
+
+class _MoEDispatch(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, src_of, slot_of):
+        ctx.save_for_backward(slot_of)
+        return _ext.get_ext().moe_dispatch(x, src_of, slot_of.shape[1])
+
+    @staticmethod
+    def backward(ctx, dxe):
+        slot_of, = ctx.saved_tensors
+        return (_ext.get_ext().moe_combine(dxe.contiguous(), None, slot_of),
+                None, None)
+
+
+def moe_dispatch(x, src_of, slot_of):
+    """x [T, h] -> [E * cap, h]: row s is x[src_of[s] // K], zeros where
+    src_of[s] is outside [0, T * K).  A bit copy.  slot_of [T, K] is the
+    inverse map of the same moe_route call; the backward sums the kept slot
+    rows of each token (dx[t] = sum_kk dxe[slot_of[t, kk]])."""
+    if _moe_native_ok(x, src_of, slot_of):
+        return _MoEDispatch.apply(x.contiguous(), src_of, slot_of)
+    T, K = slot_of.shape
+    valid = (src_of >= 0) & (src_of < T * K)
+    # through fp32 (exact both ways) so that the backward sums in fp32
+    acc = torch.promote_types(x.dtype, torch.float32)
+    return _moe_gather_rows(x.to(acc), src_of // K, valid).to(x.dtype)
+
+
+class _MoECombine(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, y, w, slot_of, src_of):
+        ctx.save_for_backward(y, w, src_of)
+        return _ext.get_ext().moe_combine(y, w, slot_of)
+
+    @staticmethod
+    def backward(ctx, dout):
+        y, w, src_of = ctx.saved_tensors
+        dy, dw = _ext.get_ext().moe_combine_bwd(y, dout.contiguous(), w, src_of)
+        return dy, dw, None, None
+
+
+def moe_combine(y, w, slot_of, src_of):
+    """y [E * cap, h], w fp32 [T, K] -> [T, h]: out[t] = sum_kk w[t, kk] *
+    y[slot_of[t, kk]] over the kk with a slot in [0, E * cap), accumulated in
+    fp32 and rounded once; a token with every choice dropped gives zeros.
+    Backward: dy[s] = w[src] * dout[t] for src = src_of[s] kept (else 0) and
+    dw[t, kk] = <y[slot], dout[t]> in fp32, 0 for a dropped entry."""
+    if _moe_native_ok(y, w, slot_of, src_of) and w.dtype == torch.float32:
+        return _MoECombine.apply(y.contiguous(), w.contiguous(), slot_of, src_of)
+    acc = torch.promote_types(y.dtype, torch.float32)
+    valid = (slot_of >= 0) & (slot_of < y.shape[0])
+    rows = _moe_gather_rows(y, slot_of, valid).to(acc)          # [T, K, h]
+    wk = torch.where(valid, w.to(acc), torch.zeros((), dtype=acc, device=w.device))
+    return (wk.unsqueeze(-1) * rows).sum(1).to(y.dtype)
+
+
+# ---------------------------------------------------------------------------
 # fused FFN: fc1(+bias+GELU in the hipBLASLt epilogue) -> fc2.
 # Backward folds dGELU + fc1 bias-grad into fc2's dgrad GEMM (DGELU_BGRAD),
 # so the [tokens, 4h] activation is never touched by a separate elementwise

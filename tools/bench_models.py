@@ -44,7 +44,32 @@ def run(name, model, make_batch, loss_fn, steps=8, warmup=3, lr=1e-4):
           f"  loss={float(loss):.3f}  peak={torch.cuda.max_memory_allocated() / 2**30:.1f} GB")
 
 
+def bench_moe(moe_dispatch):
+    """GPT-MoE 64e b8 s1024 alone, MoELayer dispatch mode as given."""
+    from paddle_amd.models import GPTPretrainingCriterion
+    from paddle_amd.models.gpt import GPTConfig
+    from paddle_amd.models.moe import GPTMoEForPretraining
+    torch.manual_seed(0)
+    cfg = GPTConfig(vocab_size=50304, hidden_size=1024, num_layers=12,
+                    num_heads=16, intermediate_size=4096, max_seq_len=1024)
+    moe = GPTMoEForPretraining(cfg, num_experts=64, k=2, moe_dispatch=moe_dispatch)
+    crit = GPTPretrainingCriterion()
+
+    def batch(dev):
+        return (torch.randint(0, cfg.vocab_size, (8, 1024), device=dev),
+                torch.randint(0, cfg.vocab_size, (8, 1024), device=dev))
+
+    run(f"gpt-moe-64e b8 s1024 dispatch={moe_dispatch}", moe, batch,
+        lambda m, b: crit(m(b[0]), b[1]))
+
+
 def main():
+    if len(sys.argv) > 1:
+        import argparse
+        ap = argparse.ArgumentParser()
+        ap.add_argument("--moe-dispatch", choices=("index", "fused"), required=True,
+                        help="run only the GPT-MoE config with this MoELayer dispatch")
+        return bench_moe(ap.parse_args().moe_dispatch)
     torch.manual_seed(0)
 
     # BERT-base: batch 64, seq 512 (classic pretraining shape)

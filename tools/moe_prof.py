@@ -1,4 +1,6 @@
-"""fp8 vs bf16 grouped-expert FFN microbench (config-5 shapes)."""
+"""fp8 vs bf16 grouped-expert FFN microbench (config-5 shapes).
+--layer index|fused: one MoELayer forward+backward instead (T 8192, h 1024,
+E 64, k 2, bf16) with that dispatch mode; --route: moe_route block forms."""
 import sys, os, time, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import paddle_amd as paddle
@@ -10,6 +12,33 @@ def bench(fn, iters=10):
     torch.cuda.synchronize(); t0 = time.perf_counter()
     for _ in range(iters): fn()
     torch.cuda.synchronize(); return (time.perf_counter() - t0) / iters * 1e3
+
+def layer_bench(mode):
+    from paddle_amd.models.moe import MoELayer
+    paddle.seed(0)
+    layer = MoELayer(1024, 4096, 64, k=2, dispatch=mode).to(
+        device="cuda", dtype=torch.bfloat16)
+    x = torch.randn(8, 1024, 1024, device="cuda", dtype=torch.bfloat16,
+                    requires_grad=True)
+    def fb():
+        (layer(x).float().sum() + layer.aux_loss).backward()
+    print(f"MoELayer f+b T8192 h1024 E64 k2 dispatch={mode}: "
+          f"{bench(fb, 20):.3f} ms", flush=True)
+
+def route_bench():
+    C = paddle._ext.get_ext()
+    topi = torch.rand(8192, 64, device="cuda").argsort(1)[:, :2].int().contiguous()
+    for waves in (1, 4, 16):
+        ms = bench(lambda: C.moe_route(topi, 64, 513, block_waves=waves), 200)
+        print(f"moe_route T8192 K2 E64 block_waves={waves}: {ms * 1e3:.1f} us/call",
+              flush=True)
+
+if "--layer" in sys.argv:
+    layer_bench(sys.argv[sys.argv.index("--layer") + 1])
+    sys.exit(0)
+if "--route" in sys.argv:
+    route_bench()
+    sys.exit(0)
 
 for N in (512, 1024, 2048):
     E, h, I = 64, 1024, 4096
