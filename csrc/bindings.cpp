@@ -510,12 +510,69 @@ static pa::FaArgs fa_dense_args(const Tensor& q, const Tensor& k, const Tensor& 
   return a;
 }
 
+// FlashMask.  startend_row_indices int32 [B, Hm, Skv, C]: (causal, C) in
+// (True, 1 | 2), (False, 2 | 4).  Returns {bounds [B, Hm, 4, Skv8], tiles
+// [B, Hm, ceil(Skv / 64), 8]} (api.h), which flash_attn_fwd / flash_attn_bwd
+// take as flashmask=(bounds, tiles) with the same `causal`.
+std::vector<Tensor> flashmask_prep(const Tensor& idx, int64_t sq, bool causal) {
+  TORCH_CHECK(idx.is_cuda() && idx.scalar_type() == torch::kInt && idx.dim() == 4,
+              "flashmask_prep: startend_row_indices must be an int32 GPU tensor [B, Hm, Skv, C]");
+  TORCH_CHECK(idx.is_contiguous(), "flashmask_prep: startend_row_indices must be contiguous");
+  const int64_t b = idx.size(0), hm = idx.size(1), skv = idx.size(2), c = idx.size(3);
+  TORCH_CHECK(causal ? (c == 1 || c == 2) : (c == 2 || c == 4),
+              "flashmask_prep: startend_row_indices has C = ", c, "; causal takes 1 or 2, "
+              "full attention 2 or 4");
+  TORCH_CHECK(b > 0 && hm > 0 && skv > 0 && sq > 0, "flashmask_prep: empty problem");
+  const int64_t skv8 = (skv + 7) / 8 * 8, ntl = (skv + 63) / 64;
+  TORCH_CHECK(sq < (1LL << 31) && idx.numel() < (1LL << 31) && b * hm * 4 * skv8 < (1LL << 31) &&
+              b * hm < 65536, "flashmask_prep: sizes must stay below 2^31 (B * Hm below 65536)");
+  auto bounds = torch::empty({b, hm, 4, skv8}, idx.options());
+  auto tiles = torch::empty({b, hm, ntl, 8}, idx.options());
+  pa::flashmask_prep(idx.const_data_ptr<int>(), bounds.mutable_data_ptr<int>(),
+                     tiles.mutable_data_ptr<int>(), b * hm, sq, skv, (int)c, causal,
+                     cur_stream());
+  return {bounds, tiles};
+}
+
+// flashmask=(bounds, tiles) of flash_attn_fwd / flash_attn_bwd: every check,
+// then the FaArgs members
+static void fa_flashmask(pa::FaArgs& a, const Tensor& q,
+                         const c10::optional<std::vector<Tensor>>& fm, bool has_mask) {
+  if (!fm.has_value()) return;
+  TORCH_CHECK(fm->size() == 2, "flash_attn: flashmask must be the (bounds, tiles) pair of "
+              "flashmask_prep");
+  const Tensor& bounds = (*fm)[0];
+  const Tensor& tiles = (*fm)[1];
+  TORCH_CHECK(!has_mask, "flash_attn: mask and flashmask exclude each other");
+  TORCH_CHECK(a.pdrop == 0.f, "flash_attn: pdrop must be 0 with flashmask");
+  for (const Tensor* t : {&bounds, &tiles}) {
+    TORCH_CHECK(t->is_cuda() && t->device() == q.device() && t->scalar_type() == torch::kInt,
+                "flash_attn: flashmask tensors must be int32 on q's GPU");
+    TORCH_CHECK(t->is_contiguous() && t->dim() == 4, "flash_attn: flashmask tensors must be "
+                "contiguous and 4-d");
+  }
+  const int64_t hm = bounds.size(1), skv8 = ((int64_t)a.skv + 7) / 8 * 8;
+  TORCH_CHECK(hm == 1 || hm == a.hkv, "flash_attn: flashmask has Hm = ", hm,
+              "; it must be 1 or HKV (", a.hkv, ")");
+  TORCH_CHECK(bounds.size(0) == a.b && bounds.size(2) == 4 && bounds.size(3) == skv8 &&
+              tiles.size(0) == a.b && tiles.size(1) == hm &&
+              tiles.size(2) == ((int64_t)a.skv + 63) / 64 && tiles.size(3) == 8,
+              "flash_attn: flashmask was prepared for another B or Skv than k's (", a.skv, ")");
+  TORCH_CHECK(bounds.numel() < (1LL << 31), "flash_attn: flashmask sizes must stay below 2^31");
+  a.fm_bounds = bounds.const_data_ptr<int>();
+  a.fm_tiles = tiles.const_data_ptr<int>();
+  a.fm_hm = (int)hm;
+  a.fm_nr = a.causal ? 1 : 2;
+}
+
 std::vector<Tensor> flash_attn_fwd(const Tensor& q, const Tensor& k, const Tensor& v,
                                    c10::optional<Tensor> o_out,
                                    double scale, bool causal,
                                    c10::optional<Tensor> mask,
-                                   double pdrop, int64_t seed, int64_t offset) {
+                                   double pdrop, int64_t seed, int64_t offset,
+                                   c10::optional<std::vector<Tensor>> flashmask) {
   pa::FaArgs a = fa_dense_args(q, k, v, scale, causal, mask, pdrop, seed, offset);
+  fa_flashmask(a, q, flashmask, mask.has_value());
   auto o = o_out.has_value() ? *o_out : torch::empty({a.b, a.h, a.sq, a.dh}, q.options());
   a.o_s = fa_view(o, "o");
   TORCH_CHECK(o.sizes() == q.sizes(), "flash_attn: o must have q's shape");
@@ -534,8 +591,12 @@ std::vector<Tensor> flash_attn_bwd(const Tensor& dout, const Tensor& q, const Te
                                    double scale, bool causal,
                                    c10::optional<Tensor> mask,
                                    double pdrop, int64_t seed, int64_t offset,
-                                   int64_t gqa_heads_per_block) {
+                                   int64_t gqa_heads_per_block,
+                                   c10::optional<std::vector<Tensor>> flashmask) {
   pa::FaArgs a = fa_dense_args(q, k, v, scale, causal, mask, pdrop, seed, offset);
+  fa_flashmask(a, q, flashmask, mask.has_value());
+  TORCH_CHECK(a.fm_bounds == nullptr || a.hkv == a.h,
+              "flash_attn_bwd: hkv != h with flashmask has no kernel (expand KV upstream)");
   auto dq = dq_out.has_value() ? *dq_out : torch::empty({a.b, a.h, a.sq, a.dh}, q.options());
   auto dk = dk_out.has_value() ? *dk_out : torch::empty({a.b, a.hkv, a.skv, a.dh}, k.options());
   auto dv = dv_out.has_value() ? *dv_out : torch::empty({a.b, a.hkv, a.skv, a.dh}, v.options());
@@ -1724,7 +1785,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("flash_attn_fwd", &flash_attn_fwd, py::arg("q"), py::arg("k"),
         py::arg("v"), py::arg("o") = c10::nullopt, py::arg("scale"),
         py::arg("causal"), py::arg("mask") = c10::nullopt,
-        py::arg("pdrop") = 0.0, py::arg("seed") = 0, py::arg("offset") = 0);
+        py::arg("pdrop") = 0.0, py::arg("seed") = 0, py::arg("offset") = 0,
+        py::arg("flashmask") = c10::nullopt);
+  m.def("flashmask_prep", &flashmask_prep, py::arg("startend_row_indices"),
+        py::arg("sq"), py::arg("causal"));
   m.def("fa_dropout_mask", &fa_dropout_mask);
   m.def("mfma_probe_fp8mx", &mfma_probe_fp8mx);
   m.def("decode_gemm_mfma", &decode_gemm_mfma, py::arg("x"), py::arg("w"),
@@ -1766,7 +1830,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("dv") = c10::nullopt, py::arg("scale"), py::arg("causal"),
         py::arg("mask") = c10::nullopt, py::arg("pdrop") = 0.0,
         py::arg("seed") = 0, py::arg("offset") = 0,
-        py::arg("gqa_heads_per_block") = 0);
+        py::arg("gqa_heads_per_block") = 0, py::arg("flashmask") = c10::nullopt);
   m.def("dropout_add_fwd", &dropout_add_fwd);
   m.def("dropout_add_bwd", &dropout_add_bwd);
   m.def("embedding_fwd", &embedding_fwd);

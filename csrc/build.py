@@ -27,6 +27,7 @@ HIP_EXTRA = {
     "sampling": _NO_PK_F32,
     "transpose": _NO_PK_F32,
     "moe_permute": _NO_PK_F32,
+    "flashmask": _NO_PK_F32,
 }
 
 

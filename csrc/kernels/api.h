@@ -145,6 +145,14 @@ void l2norm_sq(const void* x, float* out, int64_t numel, int dtype,
 // gqa_heads: q heads per dK/dV block, a divisor of h / hkv, 0 = the whole
 // group; below h / hkv the blocks write fp32 partials to gqa_ws, 2 * b *
 // (h / gqa_heads) * skv * dh floats (dK, then dV), which a reduce kernel sums.
+// FlashMask (fm_bounds != null; flashmask.hip): per key column up to two
+// half-open ranges of query rows that may not see it, on top of causal.
+// flashmask_prep writes both tensors from startend_row_indices: fm_bounds
+// int32 [b, fm_hm, 4, skv8] (lo0 | hi0 | lo1 | hi1, skv8 = skv rounded up to
+// 8), fm_tiles int32 [b, fm_hm, ceil(skv / 64), 8] (per 64-column tile and
+// range: max lo, min hi, min lo, max hi).  fm_hm is 1 or hkv (the mask head
+// of q head i is its kv head), fm_nr the ranges the form can fill (1 or 2).
+// Dense only, no additive mask, no dropout; the backward takes hkv == h.
 struct FaStride { long long b, h, s; };
 struct FaArgs {
   const void *q, *k, *v;
@@ -164,7 +172,16 @@ struct FaArgs {
   int n_qblocks, n_kvblocks;
   int gqa_heads;        // backward
   float* gqa_ws;        // backward workspace, null unless gqa_heads < h / hkv
+  const int *fm_bounds, *fm_tiles;   // FlashMask, null = none
+  int fm_hm, fm_nr;
 };
+// startend_row_indices int32 [b_hm, skv, c] -> bounds, tiles (see above); one
+// launch, no atomics, no host read, every output element written
+void flashmask_prep(const int* idx, int* bounds, int* tiles, int64_t b_hm, int64_t sq,
+                    int64_t skv, int c, bool causal, hipStream_t s);
+// what flash_attn_fwd / flash_attn_bwd (after delta) launch with fm_bounds set
+void flashmask_attn_fwd(const FaArgs& a, hipStream_t s);
+void flashmask_attn_bwd(const FaArgs& a, hipStream_t s);
 void flash_attn_fwd(const FaArgs& a, hipStream_t s);
 // delta = rowsum(dout * o), then dK / dV and dQ
 void flash_attn_bwd(const FaArgs& a, hipStream_t s);

@@ -1105,6 +1105,7 @@ __global__ __launch_bounds__(256) void fa_bwd_gqa_reduce_kernel(
 void flash_attn_bwd(const FaArgs& a, hipStream_t s) {
   const bool varlen = a.cu_q != nullptr;
   flash_attn_bwd_delta(a.dout, a.o, a.delta, a.b, a.h, a.sq, a.dh, a.do_s, a.o_s, s);
+  if (a.fm_bounds != nullptr) return flashmask_attn_bwd(a, s);   // flashmask.hip
   const int rep = a.h / a.hkv;
   const int G = a.gqa_heads > 0 ? a.gqa_heads : rep;   // q heads per dK/dV block
   const dim3 gkv((unsigned)(a.b * (a.h / G)),

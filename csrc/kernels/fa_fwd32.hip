@@ -304,6 +304,7 @@ __global__ void fa_fwd32_kernel(const FaArgs a) {
 }
 
 void flash_attn_fwd(const FaArgs& a, hipStream_t s) {
+  if (a.fm_bounds != nullptr) return flashmask_attn_fwd(a, s);   // flashmask.hip
   const bool varlen = a.cu_q != nullptr;
   const dim3 grid((unsigned)(a.b * a.h),
                   (unsigned)(varlen ? a.n_qblocks : cdiv(a.sq, 128)));

@@ -565,7 +565,15 @@ class_center_sample = _gated("class_center_sample", "PLSC-style sampling: round 
 sparse_attention = _gated("sparse_attention", "use flash_attention (dense) or paged decode")
 adaptive_log_softmax_with_loss = _gated("adaptive_log_softmax_with_loss",
                                         "use nn.AdaptiveLogSoftmaxWithLoss layer")
-flashmask_attention = _gated("flashmask_attention", "mask-sparse FA: round 2")
+
+
+def flashmask_attention(query, key, value, startend_row_indices=None, **kwargs):
+    """Flash attention under a column-sparse row-range mask ([B, S, H, D]);
+    see ops.functional.flashmask_attention."""
+    from ...ops.functional import flashmask_attention as f
+    return f(query, key, value, startend_row_indices, **kwargs)
+
+
 def flash_attn_varlen_qkvpacked(qkv, cu_seqlens, max_seqlen, dropout=0.0,
                                 causal=False, **kwargs):
     """Packed ragged QKV [total, 3, H, D] -> varlen flash attention."""

@@ -967,6 +967,156 @@ def flash_attention(q, k, v, dropout=0.0, causal=False, scale=None,
     return o, None
 
 
+# ---------------------------------------------------------------------------
+# FlashMask (csrc/kernels/flashmask.hip; docs/KERNELS.md, "FlashMask")
+# ---------------------------------------------------------------------------
+def _flashmask_ranges(idx, sq, causal):
+    """startend_row_indices [B, Hm, Skv, C] -> the canonical (lo0, hi0, lo1,
+    hi1), each [B, Hm, Skv]: query rows [lo, hi) may not see the column.
+    Clamped to [0, sq]; an empty range is (sq, sq)."""
+    c = idx.shape[-1]
+    if c not in ((1, 2) if causal else (2, 4)):
+        raise ValueError(f"flashmask_attention: startend_row_indices has C = {c}; "
+                         "causal takes 1 or 2, full attention 2 or 4")
+    col = [idx[..., i].long() for i in range(c)]
+    full, zero = torch.full_like(col[0], sq), torch.zeros_like(col[0])
+    if causal:
+        r = (col[0], col[1] if c == 2 else full, full, full)
+    elif c == 2:
+        r = (col[0], full, zero, col[1])
+    else:
+        r = tuple(col)
+    lo0, hi0, lo1, hi1 = (t.clamp(0, sq) for t in r)
+    e0, e1 = lo0 >= hi0, lo1 >= hi1
+    return (lo0.masked_fill(e0, sq), hi0.masked_fill(e0, sq),
+            lo1.masked_fill(e1, sq), hi1.masked_fill(e1, sq))
+
+
+def _flashmask_dense(idx, sq, causal):
+    """bool [B, Hm, sq, Skv], True = the score is removed (the ranges alone;
+    `causal` only names the form, the causal mask itself is not included)."""
+    lo0, hi0, lo1, hi1 = (t[:, :, None, :] for t in _flashmask_ranges(idx, sq, causal))
+    row = torch.arange(sq, device=idx.device)[:, None]
+    return ((row >= lo0) & (row < hi0)) | ((row >= lo1) & (row < hi1))
+
+
+def _flashmask_window(window_size, skv, causal, device):
+    """window_size -> startend_row_indices [1, 1, skv, C], as the reference
+    lowers it: LTS = j + left + 1 and, without causal, UTE = j - right."""
+    left, right = (window_size, window_size) if isinstance(window_size, int) else window_size
+    j = torch.arange(skv, dtype=torch.int32, device=device)
+    cols = [j + left + 1] if causal else [j + left + 1, j - right]
+    return torch.stack(cols, -1).view(1, 1, skv, len(cols))
+
+
+class _FlashMaskAttn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q, k, v, idx, scale, causal, dropout=0.0, seed=0, offset=0):
+        # q, k, v: [B, H, S, D] views; idx int32 [B, Hm, Skv, C]
+        ctx.native = _fa_native_ok(q) and dropout == 0.0
+        if ctx.native:
+            C = _ext.get_ext()
+            bounds, tiles = C.flashmask_prep(idx.to(torch.int32).contiguous(),
+                                             q.shape[2], causal)
+            o, lse = C.flash_attn_fwd(q, k, v, None, scale, causal,
+                                      flashmask=(bounds, tiles))
+            ctx.save_for_backward(q, k, v, o, lse, bounds, tiles)
+        else:
+            gone = _flashmask_dense(idx, q.shape[2], causal)
+            if gone.shape[1] not in (1, q.shape[1]):
+                gone = gone.repeat_interleave(q.shape[1] // gone.shape[1], dim=1)
+            add = torch.zeros(gone.shape, dtype=torch.float32,
+                              device=q.device).masked_fill(gone, float("-inf"))
+            dm = None
+            if dropout > 0.0:
+                g = torch.Generator(device="cpu").manual_seed(
+                    (seed * 1000003 + offset) & 0x7FFFFFFFFFFFFFFF)
+                dm = (torch.rand(q.shape[0], q.shape[1], q.shape[2], k.shape[2],
+                                 generator=g) >= dropout).to(q.device)
+            o, lse = _sdpa_ref(q, k, v, scale, causal, add, dm, dropout)
+            # a row with no visible column: O = 0, and p = exp(s - inf) = 0
+            # in the backward
+            dead = torch.isinf(lse)
+            o = o.masked_fill(dead[..., None], 0.0)
+            ctx.drop_mask = dm
+            ctx.save_for_backward(q, k, v, o, lse, add,
+                                  lse.masked_fill(dead, float("inf")))
+        ctx.scale, ctx.causal, ctx.dropout = scale, causal, dropout
+        ctx.mark_non_differentiable(lse)
+        return o, lse
+
+    @staticmethod
+    def backward(ctx, do, _dlse):
+        q, k, v, o, lse, m0, m1 = ctx.saved_tensors
+        if ctx.native:
+            C = _ext.get_ext()
+            if do.stride(-1) != 1:
+                do = do.contiguous()
+            rep = q.shape[1] // k.shape[1]
+            if rep > 1:
+                # no GQA kernel with FlashMask: expand K/V (and a per-head
+                # mask), sum the groups, as _FlashAttn does for a mask
+                k, v = (t.repeat_interleave(rep, dim=1) for t in (k, v))
+                if m0.shape[1] > 1:
+                    m0, m1 = (t.repeat_interleave(rep, dim=1) for t in (m0, m1))
+            dq, dk, dv = C.flash_attn_bwd(do, q, k, v, o, lse, scale=ctx.scale,
+                                          causal=ctx.causal, flashmask=(m0, m1))
+            if rep > 1:
+                b, h, skv, d = dk.shape
+                dk = dk.view(b, h // rep, rep, skv, d).sum(2)
+                dv = dv.view(b, h // rep, rep, skv, d).sum(2)
+        else:
+            dq, dk, dv = _sdpa_ref_bwd(do, q, k, v, m1, ctx.scale, ctx.causal, m0,
+                                       ctx.drop_mask, ctx.dropout)
+        return dq, dk, dv, None, None, None, None, None, None
+
+
+def flashmask_attention(query, key, value, startend_row_indices=None, *,
+                        dropout=0.0, causal=False, window_size=None,
+                        return_softmax_lse=False, return_seed_offset=False,
+                        fixed_seed_offset=None, rng_name="", training=True,
+                        name=None):
+    """paddle.nn.functional.flashmask_attention parity
+    (python/paddle/nn/functional/flash_attention.py).  query / key / value
+    [B, S, H, D]; startend_row_indices int32 [B, Hm, Skv, C] with Hm 1 or the
+    number of kv heads: for key column j up to two half-open ranges of query
+    rows that may not see j -- causal: C = 1 (LTS -> [LTS, Sq)) or 2 ([LTS,
+    LTE)); full: C = 2 ([LTS, Sq) and [0, UTE)) or 4 ([LTS, LTE) and [UTS,
+    UTE)).  A row that sees no column gives O = 0, LSE = -inf and no gradient.
+    window_size (int or (left, right)) is lowered to such indices and excludes
+    startend_row_indices."""
+    if window_size is not None:
+        if startend_row_indices is not None:
+            raise ValueError("flashmask_attention: window_size and "
+                             "startend_row_indices exclude each other")
+        startend_row_indices = _flashmask_window(window_size, key.shape[1], causal,
+                                                 query.device)
+    p = dropout if training else 0.0
+    seed, offset = _fa_seed_offset(fixed_seed_offset) if p > 0 else (0, 0)
+    if startend_row_indices is None:
+        out, lse = flash_attention(query, key, value, dropout=dropout, causal=causal,
+                                   return_softmax_lse=True, training=training,
+                                   fixed_seed_offset=(seed, offset) if p > 0 else None)
+    else:
+        idx = startend_row_indices
+        if idx.dim() != 4 or idx.shape[0] != query.shape[0] and idx.shape[0] != 1 \
+                or idx.shape[1] not in (1, key.shape[2]) or idx.shape[2] != key.shape[1]:
+            raise ValueError("flashmask_attention: startend_row_indices must be "
+                             "[B, 1 | HKV, Skv, C]")
+        idx = idx.expand(query.shape[0], -1, -1, -1)
+        scale = 1.0 / math.sqrt(query.shape[-1])
+        o, lse = _FlashMaskAttn.apply(query.transpose(1, 2), key.transpose(1, 2),
+                                      value.transpose(1, 2), idx, scale, causal,
+                                      p, seed, offset)
+        out = o.transpose(1, 2)
+    res = [out]
+    if return_softmax_lse:
+        res.append(lse)
+    if return_seed_offset:
+        res.append(torch.tensor([seed, offset], dtype=torch.int64))
+    return res[0] if len(res) == 1 else tuple(res)
+
+
 def scaled_dot_product_attention(query, key, value, attn_mask=None,
                                  dropout_p=0.0, is_causal=False, training=True):
     """paddle.nn.functional.scaled_dot_product_attention parity (bshd);
