@@ -1373,6 +1373,110 @@ Tensor gemm_fp8_nt_batched(const Tensor& a, const Tensor& bt, double scale_ab,
   return call.c;
 }
 
+// ---- MXFP4 GEMM (gemm_mx.hip) -------------------------------------------------
+// Contract of pa::gemm_mxfp4 / pa::mx_quant_fp4 (kernels/api.h, docs/KERNELS.md
+// "MXFP4 GEMM"): codes are staged by 16-byte accesses and scales are read as
+// byte pairs indexed by the code shape, so a scale tensor of any other shape
+// never reaches the kernel.  Everything is checked before the allocation.
+static void check_mx_operand(const char* op, const char* name, const char* sname,
+                             const Tensor& q, const Tensor& sc,
+                             const torch::Device& dev) {
+  TORCH_CHECK(q.is_cuda() && q.device() == dev, op, ": ", name,
+              " must be a GPU tensor on the device of a");
+  TORCH_CHECK(sc.is_cuda() && sc.device() == dev, op, ": ", sname,
+              " must be a GPU tensor on the device of a");
+  TORCH_CHECK(q.scalar_type() == torch::kUInt8, op, ": ", name, " must be uint8 codes");
+  TORCH_CHECK(sc.scalar_type() == torch::kUInt8, op, ": ", sname,
+              " must be uint8 e8m0 scales");
+  TORCH_CHECK(q.dim() == 2 && q.stride(1) == 1, op, ": ", name,
+              " must be 2-D [rows, K/2] with unit inner stride");
+  const int64_t rows = q.size(0), k = q.size(1) * 2;
+  TORCH_CHECK(k % 128 == 0 && k >= 128, op, ": K must be a multiple of 128 and >= 128, ",
+              name, " has K = ", k);
+  TORCH_CHECK(sc.dim() == 2 && sc.size(0) == rows && sc.size(1) == k / 32 &&
+              sc.stride(1) == 1, op, ": ", sname, " must be [", rows, ", ", k / 32,
+              "] (one scale per 32 elements of ", name, ") with unit inner stride");
+  TORCH_CHECK(q.stride(0) % 16 == 0 && aligned16(q), op, ": ", name,
+              " rows and data must be 16-byte aligned");
+  TORCH_CHECK(sc.stride(0) % 2 == 0 &&
+              reinterpret_cast<uintptr_t>(sc.const_data_ptr()) % 2 == 0, op, ": ",
+              sname, " row stride and data must be 2-byte aligned");
+}
+
+Tensor gemm_mxfp4_nt(const Tensor& a, const Tensor& a_scale, const Tensor& bt,
+                     const Tensor& bt_scale, const c10::optional<Tensor>& bias) {
+  const char* op = "gemm_mxfp4_nt";
+  TORCH_CHECK(a.is_cuda(), op, ": a must be a GPU tensor");
+  check_mx_operand(op, "a", "a_scale", a, a_scale, a.device());
+  check_mx_operand(op, "bt", "bt_scale", bt, bt_scale, a.device());
+  const int64_t m = a.size(0), n = bt.size(0), k = a.size(1) * 2;
+  const int64_t lim = int64_t(1) << 31;
+  TORCH_CHECK(bt.size(1) * 2 == k, op, ": inner dims of a and bt must agree, got K = ",
+              k, " and ", bt.size(1) * 2);
+  TORCH_CHECK(m >= 1 && n >= 1 && m < lim && n < lim && k < lim, op,
+              ": 1 <= M, N and K < 2^31, got ", m, ", ", n, ", ", k);
+  pa::GemmArgs g{};
+  if (bias.has_value()) {
+    TORCH_CHECK(bias->device() == a.device(), op, ": bias must be on the device of a");
+    TORCH_CHECK(bias->scalar_type() == torch::kBFloat16 && bias->is_contiguous() &&
+                bias->dim() == 1 && bias->size(0) == n, op,
+                ": bias must be contiguous bfloat16 [N]");
+    g.bias = bias->const_data_ptr();
+  }
+  auto c = torch::empty({m, n}, a.options().dtype(torch::kBFloat16));
+  g.a = a.const_data_ptr();
+  g.b = bt.const_data_ptr();
+  g.c = c.mutable_data_ptr();
+  g.m = m; g.n = n; g.k = k;
+  g.lda = a.stride(0); g.ldb = bt.stride(0); g.ldc = n;
+  g.batch = 1;
+  pa::gemm_mxfp4(g, a_scale.const_data_ptr<uint8_t>(),
+                 bt_scale.const_data_ptr<uint8_t>(), a_scale.stride(0),
+                 bt_scale.stride(0), cur_stream());
+  return c;
+}
+
+std::vector<Tensor> mx_quant_fp4(const Tensor& x) {
+  const char* op = "mx_quant_fp4";
+  TORCH_CHECK(x.is_cuda(), op, ": x must be a GPU tensor");
+  TORCH_CHECK(x.scalar_type() == torch::kBFloat16, op, ": x must be bfloat16");
+  TORCH_CHECK(x.dim() == 2 && x.stride(1) == 1, op,
+              ": x must be 2-D with unit inner stride");
+  const int64_t rows = x.size(0), k = x.size(1);
+  TORCH_CHECK(rows >= 1 && k >= 32 && k % 32 == 0 && k < (int64_t(1) << 31), op,
+              ": x must be [rows >= 1, K] with K a multiple of 32 below 2^31, got [",
+              rows, ", ", k, "]");
+  TORCH_CHECK(x.stride(0) % 8 == 0 && aligned16(x), op,
+              ": x row stride must be a multiple of 8 elements and its data "
+              "16-byte aligned");
+  auto opts = x.options().dtype(torch::kUInt8);
+  auto codes = torch::empty({rows, k / 2}, opts);
+  auto scales = torch::empty({rows, k / 32}, opts);
+  pa::mx_quant_fp4(x.const_data_ptr(), codes.mutable_data_ptr(),
+                   scales.mutable_data_ptr(), rows, k, x.stride(0), cur_stream());
+  return {codes, scales};
+}
+
+Tensor mfma_probe_fp4mx(const Tensor& a, const Tensor& bt, const Tensor& sa,
+                        const Tensor& sb, int64_t opsel) {
+  const char* op = "mfma_probe_fp4mx";
+  for (const Tensor* t : {&a, &bt, &sa, &sb})
+    TORCH_CHECK(t->is_cuda() && t->is_contiguous() &&
+                t->scalar_type() == torch::kUInt8 && t->device() == a.device(), op,
+                ": a, bt, sa, sb must be contiguous uint8 tensors on one GPU");
+  TORCH_CHECK(a.numel() == 16 * 64 && bt.numel() == 16 * 64, op,
+              ": a and bt must be [16, 64]");
+  TORCH_CHECK(sa.numel() == 16 * 4 && sb.numel() == 16 * 4, op,
+              ": sa and sb must be [16, 4]");
+  TORCH_CHECK(aligned16(a) && aligned16(bt), op, ": a and bt must be 16-byte aligned");
+  TORCH_CHECK(opsel >= 0 && opsel <= 3, op, ": opsel must be 0..3, got ", opsel);
+  auto c = torch::empty({16, 16}, a.options().dtype(torch::kFloat));
+  pa::mfma_probe_fp4mx(a.const_data_ptr(), bt.const_data_ptr(), sa.const_data_ptr(),
+                       sb.const_data_ptr(), c.mutable_data_ptr<float>(), (int)opsel,
+                       cur_stream());
+  return c;
+}
+
 // Contract of the MFMA W-streamer (decode_stream_kernel, docs/KERNELS.md),
 // shared by decode_gemm_mfma / _int8 / _int4: every lane does 16-byte loads
 // of whole 64 x 256 weight tiles and of x rows, so shapes, placement and base
@@ -1813,6 +1917,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("scale_ab") = 1.0, py::arg("bias") = c10::nullopt);
   m.def("gemm_fp8_nt_batched", &gemm_fp8_nt_batched, py::arg("a"),
         py::arg("bt"), py::arg("scale_ab"), py::arg("bias") = c10::nullopt);
+  m.def("gemm_mxfp4_nt", &gemm_mxfp4_nt, py::arg("a"), py::arg("a_scale"),
+        py::arg("bt"), py::arg("bt_scale"), py::arg("bias") = c10::nullopt);
+  m.def("mx_quant_fp4", &mx_quant_fp4, py::arg("x"));
+  m.def("mfma_probe_fp4mx", &mfma_probe_fp4mx, py::arg("a"), py::arg("bt"),
+        py::arg("sa"), py::arg("sb"), py::arg("opsel"));
   m.def("amax_abs", &amax_abs);
   m.def("quant_fp8", &quant_fp8);
   m.def("flash_attn_varlen_fwd", &flash_attn_varlen_fwd, py::arg("q"),

@@ -28,6 +28,7 @@ HIP_EXTRA = {
     "transpose": _NO_PK_F32,
     "moe_permute": _NO_PK_F32,
     "flashmask": _NO_PK_F32,
+    "gemm_mx": _NO_PK_F32,
 }
 
 

@@ -364,6 +364,38 @@ void gemm_fp8(const GemmArgs& g, hipStream_t s);
 void quant_fp8(const void* x, void* out, float scale, int64_t numel,
                hipStream_t s);
 
+// ---- MXFP4 GEMM (gemm_mx.hip) -----------------------------------------------
+// OCP microscaling fp4.  codes uint8 [R, K/2]: byte i of a row holds element
+// 2i in the low nibble and 2i+1 in the high one (e2m1: sign, 2-bit exponent,
+// 1-bit mantissa; magnitudes 0 .5 1 1.5 2 3 4 6).  scales uint8 [R, K/32]
+// e8m0, one per 32 elements along K: 2^(byte - 127).
+// gemm_mxfp4: C[m][n] = sum_k A[m][k] * Bt[n][k] (+ bias[n]), fp32
+//   accumulate, bf16 C.  Reads of GemmArgs: a, b (codes), c, bias, m, n, k
+//   (ELEMENTS), lda / ldb (BYTES of codes per row), ldc; batch must be 1;
+//   scale_ab, epilogue, layout, accumulate and aux are not read.  sa [m][k/32]
+//   and sb [n][k/32] with row strides ldsa / ldsb in bytes.
+// Contract (checked by the binding before any launch or allocation):
+//   * everything on one GPU; codes and scales uint8 with unit inner stride;
+//   * code rows (lda, ldb) and the a / b base pointers 16-byte aligned; ldsa,
+//     ldsb and the sa / sb base pointers even (the kernel loads scale pairs);
+//   * k % 128 == 0, 128 <= k < 2^31, 1 <= m, n < 2^31; bias bf16 [n] or null.
+//   * k % 256 != 0 runs the guarded kernel over the whole grid (slow path).
+// mx_quant_fp4: x bf16 [rows, k] with row stride ld elements (ld % 8 == 0,
+//   base 16-byte aligned, k % 32 == 0, finite values) -> contiguous codes
+//   [rows, k/2] and scales [rows, k/32].  Per block: e = floor(log2 amax) - 2
+//   from the exponent bits of amax, clamped to [-127, 127]; scale byte e +
+//   127; amax == 0 gives byte 127 and zero codes; each element is x * 2^-e
+//   rounded to the nearest grid value, ties to the even code, saturating at 6.
+//   One read pass, no atomics, no workspace, no host read.
+void gemm_mxfp4(const GemmArgs& g, const uint8_t* sa, const uint8_t* sb,
+                int64_t ldsa, int64_t ldsb, hipStream_t s);
+void mx_quant_fp4(const void* x, void* codes, void* scales, int64_t rows,
+                  int64_t k, int64_t ld, hipStream_t s);
+// one-wave layout probe of the e2m1 scaled MFMA: a, bt [16][64] codes, sa, sb
+// [16][4] scale bytes, c [16][16] fp32, opsel 0..3 the scale byte position
+void mfma_probe_fp4mx(const void* a, const void* bt, const void* sa,
+                      const void* sb, float* c, int opsel, hipStream_t s);
+
 // MFMA W-streaming decode GEMMs (decode_gemm.hip) for three weight formats.  1 <= M <= 32, N % 256 == 0, K % 64 == 0, K <= 2^24;
 // x bf16 [M, K] contiguous; x and weight base pointers 16-byte aligned.
 // ksplit 0 = heuristic.  `workspace` holds [decode_split_plan(k, n,

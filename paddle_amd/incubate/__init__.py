@@ -3,6 +3,7 @@ from . import autograd  # noqa: F401
 from . import multiprocessing  # noqa: F401
 from . import autotune  # noqa: F401
 from . import fp8  # noqa: F401
+from . import mx  # noqa: F401
 from . import nn  # noqa: F401
 
 # graph / segment ops + optimizer wrappers (reference: incubate/__init__.py)

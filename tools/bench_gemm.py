@@ -70,6 +70,11 @@ def main():
     ap.add_argument("--custom", action="store_true")
     ap.add_argument("--autotune", action="store_true")
     ap.add_argument("--fp8", action="store_true")
+    ap.add_argument("--mxfp4", action="store_true",
+                    help="MXFP4 GEMM vs fp8 and bf16, and the two quantizers")
+    ap.add_argument("--mx-out", default=os.path.join(
+        os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
+        "profiles", "gemm_mx.txt"))
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--wgrad-layout", action="store_true",
                     help="wgrad by operand layout at the flagship shapes")
@@ -86,6 +91,9 @@ def main():
         return
     if args.fp8:
         bench_fp8()
+        return
+    if args.mxfp4:
+        bench_mxfp4(args.iters, args.mx_out)
         return
     if args.custom:
         bench_custom()
@@ -315,6 +323,73 @@ def bench_fp8():
               f"(relerr {err:.1e})")
         del x, w, qx, qwt
         torch.cuda.empty_cache()
+
+
+def bench_mxfp4(iters, out_path, rounds=2):
+    """gemm_mxfp4_nt vs gemm_fp8_nt vs the bf16 dispatch on the same (M, N, K),
+    and mx_quant_fp4 vs quant_fp8 + amax_abs.  Every entry is timed in
+    `rounds` alternating rounds by device events; a win is a mean below the
+    other side's minimum in every round."""
+    from paddle_amd import _ext
+    from paddle_amd.incubate import mx
+    C = _ext.get_ext()
+    lines = []
+
+    def emit(s):
+        print(s, flush=True)
+        lines.append(s)
+
+    def run(cases):
+        res = {tag: [] for tag, _ in cases}
+        for r in range(rounds):
+            for tag, fn in (cases if r % 2 == 0 else cases[::-1]):
+                ms = _times_ms(fn, iters)
+                res[tag].append((sum(ms) / len(ms), min(ms)))
+        return res
+
+    emit(f"# {torch.cuda.get_device_name(0)}  iters {iters}  rounds {rounds}  "
+         f"ms as mean/min per round, order reversed in odd rounds")
+    shapes = [("8k3", 8192, 8192, 8192)] + SHAPES_B8[:4] + SHAPES_LLAMA
+    for name, M, K, N in shapes:
+        x = torch.randn(M, K, device="cuda", dtype=torch.bfloat16)
+        wt = torch.randn(N, K, device="cuda", dtype=torch.bfloat16) * 0.02
+        qx, sx = mx.mx_quantize(x)
+        qw, sw = mx.mx_quantize(wt)
+        x8, w8 = x.to(torch.float8_e4m3fn), wt.to(torch.float8_e4m3fn)
+        # same operands through torch: the fp4 product is a bf16-exact input
+        ref = torch.matmul(mx.mx_dequantize(qx, sx, torch.bfloat16),
+                           mx.mx_dequantize(qw, sw, torch.bfloat16).t())
+        err = _check(C.gemm_mxfp4_nt(qx, sx, qw, sw), ref.float(), f"{name} mxfp4")
+        del ref
+        w = wt.t()
+        res = run([("mxfp4", lambda: C.gemm_mxfp4_nt(qx, sx, qw, sw)),
+                   ("fp8", lambda: C.gemm_fp8_nt(x8, w8, 1.0)),
+                   ("bf16", lambda: torch.matmul(x, w))])
+        flops = 2.0 * M * K * N
+        for tag in ("mxfp4", "fp8", "bf16"):
+            rr = "  ".join(f"{m:8.4f}/{lo:8.4f}" for m, lo in res[tag])
+            emit(f"{name:10s} M{M} N{N} K{K} {tag:6s} {rr}  "
+                 f"{flops / res[tag][0][0] / 1e9:7.1f} TF  (relerr {err:.1e})")
+        win = all(res["mxfp4"][r][0] < res["fp8"][r][1] for r in range(rounds))
+        emit(f"{name:10s} mxfp4 mean < fp8 min in every round: {win}")
+        del x, wt, w, qx, sx, qw, sw, x8, w8
+        torch.cuda.empty_cache()
+
+    x = torch.randn(24576, 4096, device="cuda", dtype=torch.bfloat16)
+
+    def q8():
+        ax = C.amax_abs(x).clamp(min=1e-12)
+        return C.quant_fp8(x, float(448.0 / ax))
+
+    res = run([("mx_quant_fp4", lambda: C.mx_quant_fp4(x)),
+               ("amax+quant_fp8", q8)])
+    for tag, rr in res.items():
+        emit(f"quant [24576, 4096] {tag:16s} " +
+             "  ".join(f"{m:8.4f}/{lo:8.4f}" for m, lo in rr) +
+             f"  {x.numel() * 2 / rr[0][0] / 1e6:7.1f} GB/s read")
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "w") as f:
+        f.write("\n".join(lines) + "\n")
 
 
 if __name__ == "__main__":
