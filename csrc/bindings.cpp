@@ -1609,6 +1609,90 @@ Tensor dequant_int4(const Tensor& qw, const Tensor& scale, int64_t group_size,
   return out;
 }
 
+// ---- MXFP4 weight-only decode streamer (decode_gemm_mx.hip) --------------------
+// Contract of pa::decode_gemm_mxfp4 (kernels/api.h, docs/KERNELS.md "MXFP4
+// decode streamer"): every lane does 16-byte loads of x and of the code rows
+// and 4-byte loads of the scale rows, addressed from the shapes alone, so
+// placement, dtypes, exact shapes and base alignment are checked here, before
+// the allocations and the launch.
+static bool aligned_to(const Tensor& t, uintptr_t a) {
+  return reinterpret_cast<uintptr_t>(t.const_data_ptr()) % a == 0;
+}
+
+Tensor decode_gemm_mxfp4(const Tensor& x, const Tensor& qweight,
+                         const Tensor& weight_scale,
+                         const c10::optional<Tensor>& bias, int64_t ksplit) {
+  const char* op = "decode_gemm_mxfp4";
+  TORCH_CHECK(x.is_cuda(), op, ": x must be a GPU tensor");
+  TORCH_CHECK(qweight.is_cuda() && qweight.device() == x.device(), op,
+              ": qweight must be a GPU tensor on the device of x");
+  TORCH_CHECK(weight_scale.is_cuda() && weight_scale.device() == x.device(), op,
+              ": weight_scale must be a GPU tensor on the device of x");
+  TORCH_CHECK(x.scalar_type() == torch::kBFloat16 && x.dim() == 2 &&
+              x.is_contiguous(), op, ": x must be a contiguous bf16 [M, K] tensor");
+  TORCH_CHECK(qweight.scalar_type() == torch::kUInt8 && qweight.dim() == 2 &&
+              qweight.is_contiguous(), op,
+              ": qweight must be contiguous uint8 codes [N, K/2]");
+  const int64_t m = x.size(0), k = x.size(1), n = qweight.size(0);
+  TORCH_CHECK(m >= 1 && m <= 32, op, ": x must have 1 <= M <= 32 rows, got ", m);
+  TORCH_CHECK(k % 128 == 0 && k >= 128 && k <= (int64_t(1) << 24), op,
+              ": K % 128 == 0 and 128 <= K <= 2^24, x has K = ", k);
+  TORCH_CHECK(qweight.size(1) * 2 == k, op, ": qweight must be [N, K/2] with K = ",
+              k, " of x, got K = ", qweight.size(1) * 2);
+  TORCH_CHECK(n >= 64 && n % 64 == 0, op,
+              ": N % 64 == 0 and N >= 64, qweight has N = ", n);
+  TORCH_CHECK(weight_scale.scalar_type() == torch::kUInt8 &&
+              weight_scale.dim() == 2 && weight_scale.size(0) == n &&
+              weight_scale.size(1) == k / 32 && weight_scale.is_contiguous(), op,
+              ": weight_scale must be contiguous uint8 e8m0, exactly [", n, ", ",
+              k / 32, "]");
+  TORCH_CHECK(aligned16(x), op, ": x data must be 16-byte aligned");
+  TORCH_CHECK(aligned16(qweight), op, ": qweight data must be 16-byte aligned");
+  TORCH_CHECK(aligned_to(weight_scale, 4), op,
+              ": weight_scale data must be 4-byte aligned");
+  TORCH_CHECK(ksplit >= 0, op, ": ksplit >= 0, got ", ksplit);
+  const void* bp = nullptr;
+  if (bias.has_value()) {
+    TORCH_CHECK(bias->is_cuda() && bias->device() == x.device() &&
+                bias->scalar_type() == torch::kBFloat16 && bias->is_contiguous() &&
+                bias->dim() == 1 && bias->size(0) == n, op,
+                ": bias must be contiguous bf16 [N] on the device of x");
+    bp = bias->const_data_ptr();
+  }
+  const int64_t splits = pa::decode_mx_split_plan(k, n, ksplit).splits;
+  auto ws = torch::empty({splits, m <= 16 ? 16 : 32, n},
+                         x.options().dtype(torch::kFloat));
+  auto y = torch::empty({m, n}, x.options());
+  pa::decode_gemm_mxfp4(x.const_data_ptr(), qweight.const_data_ptr(),
+                        weight_scale.const_data_ptr(), bp, y.mutable_data_ptr(),
+                        ws.mutable_data_ptr<float>(), m, n, k, ksplit,
+                        cur_stream());
+  return y;
+}
+
+// codes [R, K/2] + scales [R, K/32] -> bf16 [R, K]
+Tensor mx_dequant_fp4(const Tensor& codes, const Tensor& scales) {
+  const char* op = "mx_dequant_fp4";
+  TORCH_CHECK(codes.is_cuda(), op, ": codes must be a GPU tensor");
+  TORCH_CHECK(scales.is_cuda() && scales.device() == codes.device(), op,
+              ": scales must be a GPU tensor on the device of codes");
+  TORCH_CHECK(codes.scalar_type() == torch::kUInt8 && codes.dim() == 2 &&
+              codes.is_contiguous() && codes.size(0) >= 1 && codes.size(1) >= 16 &&
+              codes.size(1) % 16 == 0, op,
+              ": codes must be contiguous uint8 [R, K/2] with K a multiple of 32");
+  const int64_t rows = codes.size(0), k = codes.size(1) * 2;
+  TORCH_CHECK(scales.scalar_type() == torch::kUInt8 && scales.dim() == 2 &&
+              scales.size(0) == rows && scales.size(1) == k / 32 &&
+              scales.is_contiguous(), op,
+              ": scales must be contiguous uint8 e8m0, exactly [", rows, ", ",
+              k / 32, "]");
+  TORCH_CHECK(aligned16(codes), op, ": codes data must be 16-byte aligned");
+  auto out = torch::empty({rows, k}, codes.options().dtype(torch::kBFloat16));
+  pa::mx_dequant_fp4(codes.const_data_ptr(), scales.const_data_ptr(),
+                     out.mutable_data_ptr(), rows, k, cur_stream());
+  return out;
+}
+
 // ---- MoE routing ----------------------------------------------------------
 std::vector<Tensor> moe_gate_topk(const Tensor& logits, int64_t k) {
   CHECK_IN(logits);
@@ -1904,6 +1988,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("group_size") = -1, py::arg("ksplit") = 0);
   m.def("dequant_int4", &dequant_int4, py::arg("qw"), py::arg("scale"),
         py::arg("group_size"), py::arg("out_dtype"));
+  m.def("decode_gemm_mxfp4", &decode_gemm_mxfp4, py::arg("x"),
+        py::arg("qweight"), py::arg("weight_scale"),
+        py::arg("bias") = c10::nullopt, py::arg("ksplit") = 0);
+  m.def("mx_dequant_fp4", &mx_dequant_fp4, py::arg("codes"), py::arg("scales"));
   m.def("moe_gate_topk", &moe_gate_topk);
   m.def("moe_assign_slots", &moe_assign_slots);
   m.def("moe_route", &moe_route, py::arg("topi"), py::arg("num_experts"),

@@ -29,6 +29,7 @@ HIP_EXTRA = {
     "moe_permute": _NO_PK_F32,
     "flashmask": _NO_PK_F32,
     "gemm_mx": _NO_PK_F32,
+    "decode_gemm_mx": _NO_PK_F32,
 }
 
 

@@ -423,6 +423,35 @@ void decode_gemm_int4(const void* x, const void* qw, const float* scale,
 void dequant_int4(const void* qw, const float* scale, void* out, int64_t k,
                   int64_t n, int64_t group_size, int dtype, hipStream_t s);
 
+// ---- MXFP4 weight-only decode streamer (decode_gemm_mx.hip) -----------------
+// decode_gemm_mxfp4: y[M,N] = x[M,K] . dequant(qw, scales)^T (+ bias[N]); x, y,
+//   bias bf16, fp32 accumulate; only the weight is fp4 (x is not quantized).
+//   qw / scales in the MXFP4 GEMM format above with R = N: codes [N, K/2],
+//   e8m0 scales [N, K/32].  `workspace` holds [decode_mx_split_plan(k, n,
+//   ksplit).splits, padded_m, N] fp32 with padded_m = 16 (M <= 16) or 32; rows
+//   < M of it are written in full before the reduce kernel reads them.
+//   ksplit 0 = heuristic; kchunk is a multiple of 128.  No atomics, no host
+//   read.
+// Contract (checked by the binding before any launch or allocation):
+//   * everything on one GPU;
+//   * x bf16 [M, K] contiguous and 16-byte aligned, 1 <= M <= 32;
+//   * qw uint8 [N, K/2] contiguous and 16-byte aligned;
+//   * scales uint8, exactly [N, K/32], contiguous and 4-byte aligned;
+//   * K % 128 == 0, 128 <= K <= 2^24; N % 64 == 0, N >= 64;
+//   * bias bf16 contiguous [N] or null; ksplit >= 0.
+//   * scale bytes in [8, 247] (what mx_quant_fp4 writes for bf16-normal
+//     weights; not scanned): inside it every weight is converted exactly,
+//     outside it the result is unspecified but memory-safe.
+// mx_dequant_fp4: codes [rows, k/2] + scales [rows, k/32], both contiguous,
+//   codes 16-byte aligned, k % 32 == 0 -> out bf16 [rows, k] contiguous;
+//   exact for the same scale range.
+DecodeSplitPlan decode_mx_split_plan(int64_t k, int64_t n, int64_t ksplit);
+void decode_gemm_mxfp4(const void* x, const void* qw, const void* scales,
+                       const void* bias, void* y, float* workspace, int64_t m,
+                       int64_t n, int64_t k, int64_t ksplit, hipStream_t s);
+void mx_dequant_fp4(const void* codes, const void* scales, void* out,
+                    int64_t rows, int64_t k, hipStream_t s);
+
 // ---- MoE routing (assign_pos/number_count/gate parity) --------------------
 void moe_gate_topk(const float* logits, float* topv, int* topi, float* me,
                    float* ce, int64_t t, int64_t e, int64_t k, hipStream_t s);

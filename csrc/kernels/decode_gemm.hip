@@ -13,6 +13,7 @@
 // by all of them, reduces + adds bias + casts to bf16.
 #include "common.h"
 #include "api.h"
+#include "decode_gemm.h"
 #include "int4_codes.h"
 
 namespace pa {
@@ -38,9 +39,10 @@ __global__ void decode_gemm_reduce_kernel(const float* __restrict__ partial,
   y[i] = f2bf(acc);
 }
 
-static void launch_reduce(const float* workspace, const float* chscale,
-                          float qinv, const void* bias, void* y, int64_t m,
-                          int64_t n, int mt, int splits, hipStream_t s) {
+void decode_gemm_launch_reduce(const float* workspace, const float* chscale,
+                               float qinv, const void* bias, void* y,
+                               int64_t m, int64_t n, int mt, int splits,
+                               hipStream_t s) {
   long long total = m * n;
   dim3 rg((unsigned)((total + 255) / 256));
   hipLaunchKernelGGL(decode_gemm_reduce_kernel, rg, dim3(256), 0, s, workspace,
@@ -519,7 +521,8 @@ static void launch_stream(StreamKernel k16, StreamKernel k32, const void* x,
   hipLaunchKernelGGL(mt == 16 ? k16 : k32, grid, dim3(256), 0, s,
                      (const short*)x, w, gscale, workspace, (int)m, (int)n,
                      (int)k, (long long)ldw, gshift, plan.kchunk);
-  launch_reduce(workspace, chscale, qinv, bias, y, m, n, mt, plan.splits, s);
+  decode_gemm_launch_reduce(workspace, chscale, qinv, bias, y, m, n, mt,
+                            plan.splits, s);
 }
 
 void decode_gemm_mfma(const void* x, const void* w, const void* bias, void* y,

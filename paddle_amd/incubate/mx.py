@@ -78,11 +78,20 @@ def mxfp4_gemm_nt(qa, sa, qb, sb, bias=None):
 
 
 class MXFP4Linear(torch.nn.Module):
-    """Linear whose weight is held in MXFP4 and whose forward runs the fp4
-    GEMM on activations quantized per call.  Inference only."""
+    """Linear whose weight is held in MXFP4.  Inference only.
 
-    def __init__(self, qweight, weight_scale, bias=None):
+    activation="mxfp4" (default): the forward quantizes the activations per
+    call and runs the fp4 GEMM.  activation="bf16": the activations stay bf16
+    (W4A16) and the forward is quantization.weight_only_linear(weight_dtype=
+    "mxfp4") -- the decode W-streamer for up to 32 rows, dequantize + linear
+    above that."""
+
+    def __init__(self, qweight, weight_scale, bias=None, activation="mxfp4"):
         super().__init__()
+        if activation not in ("mxfp4", "bf16"):
+            raise ValueError("MXFP4Linear: activation must be 'mxfp4' or 'bf16', "
+                             f"got {activation!r}")
+        self.activation = activation
         self.out_features = qweight.shape[0]
         self.in_features = qweight.shape[1] * 2
         self.register_buffer("qweight", qweight)            # [out, in/2]
@@ -90,7 +99,7 @@ class MXFP4Linear(torch.nn.Module):
         self.register_buffer("bias", bias)
 
     @classmethod
-    def from_linear(cls, linear):
+    def from_linear(cls, linear, activation="mxfp4"):
         """From a paddle-layout Linear (weight [in, out]), quantized once along in."""
         w = linear.weight.detach()
         if w.dim() != 2 or w.shape[0] % 128 != 0:
@@ -100,12 +109,16 @@ class MXFP4Linear(torch.nn.Module):
         b = getattr(linear, "bias", None)
         if b is not None:
             b = b.detach().to(torch.bfloat16).contiguous()
-        return cls(q, s, b)
+        return cls(q, s, b, activation=activation)
 
     def forward(self, x):
         if torch.is_grad_enabled() and x.requires_grad:
             raise RuntimeError("MXFP4Linear is forward only: the input requires "
                                "grad; run it under torch.no_grad() or detach it")
+        if self.activation == "bf16":
+            from ..quantization import weight_only_linear
+            return weight_only_linear(x, self.qweight, self.weight_scale,
+                                      self.bias, weight_dtype="mxfp4")
         x2 = x.reshape(-1, self.in_features)
         if x2.is_cuda:
             qx, sx = mx_quantize(x2.to(torch.bfloat16))
@@ -118,13 +131,15 @@ class MXFP4Linear(torch.nn.Module):
         return out.to(x.dtype).reshape(*x.shape[:-1], self.out_features)
 
     def extra_repr(self):
-        return f"in={self.in_features}, out={self.out_features}, mxfp4"
+        return (f"in={self.in_features}, out={self.out_features}, mxfp4, "
+                f"activation={self.activation}")
 
 
-def convert_linears_to_mxfp4(model, min_features=256, skip=("lm_head",)):
-    """Replace paddle Linear layers by MXFP4Linear in place (weights quantized
-    once).  Small layers, skipped names and layers whose `in` is not a multiple
-    of 128 are left alone.  Returns the converted count."""
+def convert_linears_to_mxfp4(model, min_features=256, skip=("lm_head",),
+                             activation="mxfp4"):
+    """Replace paddle Linear layers by MXFP4Linear(activation=...) in place
+    (weights quantized once).  Small layers, skipped names and layers whose
+    `in` is not a multiple of 128 are left alone.  Returns the converted count."""
     todo = []
     for name, mod in model.named_modules():
         if type(mod).__name__ != "Linear" or not hasattr(mod, "weight"):
@@ -138,5 +153,6 @@ def convert_linears_to_mxfp4(model, min_features=256, skip=("lm_head",)):
     for name in todo:
         parent_name, _, child = name.rpartition(".")
         parent = model.get_submodule(parent_name) if parent_name else model
-        setattr(parent, child, MXFP4Linear.from_linear(getattr(parent, child)))
+        setattr(parent, child, MXFP4Linear.from_linear(getattr(parent, child),
+                                                       activation=activation))
     return len(todo)

@@ -226,21 +226,22 @@ def _mk(cls_or_inst):
         return BaseQuanter()
 
 
-# -- weight-only int8 / int4 (serving decode path) ---------------------------
+# -- weight-only int8 / int4 / mxfp4 (serving decode path) -------------------
 # parity: paddle/phi/kernels/weight_quantize_kernel.cu + funcs/weight_only_gemv.cu
-_WO_ALGOS = {"weight_only_int8": "int8", "weight_only_int4": "int4"}
+_WO_ALGOS = {"weight_only_int8": "int8", "weight_only_int4": "int4",
+             "weight_only_mxfp4": "mxfp4"}
 _WO_GROUP_SIZES = (-1, 64, 128)
 
 
 def _wo_check(algo=None, weight_dtype=None, group_size=-1):
-    """Validate the weight-only arguments; returns "int8" | "int4"."""
+    """Validate the weight-only arguments; returns "int8" | "int4" | "mxfp4"."""
     if algo is not None:
         if algo not in _WO_ALGOS:
             raise ValueError(f"unknown weight-only algo {algo!r}; expected one "
                              f"of {sorted(_WO_ALGOS)}")
         weight_dtype = _WO_ALGOS[algo]
-    if weight_dtype not in ("int8", "int4"):
-        raise ValueError(f"weight_dtype must be 'int8' or 'int4', got "
+    if weight_dtype not in ("int8", "int4", "mxfp4"):
+        raise ValueError(f"weight_dtype must be 'int8', 'int4' or 'mxfp4', got "
                          f"{weight_dtype!r}")
     if group_size not in _WO_GROUP_SIZES:
         raise ValueError(f"group_size must be one of {_WO_GROUP_SIZES}, got "
@@ -248,6 +249,9 @@ def _wo_check(algo=None, weight_dtype=None, group_size=-1):
     if weight_dtype == "int8" and group_size != -1:
         raise NotImplementedError("int8 weight-only supports per-channel "
                                   "scales only (group_size=-1)")
+    if weight_dtype == "mxfp4" and group_size != -1:
+        raise NotImplementedError("mxfp4 weight-only carries its own e8m0 scale "
+                                  "per 32 elements (group_size=-1)")
     return weight_dtype
 
 
@@ -269,11 +273,20 @@ def weight_quantize(w, algo="weight_only_int8", group_size=-1):
         nibbles, even k in the low nibble.
     Dequantization evaluates q * (scale * fp32(1/7)) in fp32.
 
+    weight_only_mxfp4 (K % 32 == 0): mx_quantize(w.t()) of incubate.mx --
+    qweight uint8 e2m1 codes [N, K/2], scale uint8 e8m0 [N, K/32], one per
+    32 elements along K.  This layout is N-MAJOR (one output channel per
+    row, K contiguous), unlike int8 and int4: an MX block is contiguous in
+    memory and one 16-byte load of the decode streamer is one block.
+
     The [K, N]-derived layouts feed the MFMA W-streaming decode kernels
     with coalesced rows (the round-1 [N, K] GEMV layout read 180-330 GB/s;
     the streamer reads at the memory roofline on HALF the bytes)."""
     import torch
     wd = _wo_check(algo=algo, group_size=group_size)
+    if wd == "mxfp4":
+        from ..incubate.mx import mx_quantize
+        return mx_quantize(w.detach().t().contiguous())
     wf = w.detach().float()                          # [K, N]
     if wd == "int8":
         scale = wf.abs().amax(dim=0).clamp(min=1e-8)     # [N]
@@ -373,16 +386,79 @@ def _wo_int8_native_ok(x, qweight, scale, bias=None):
             and _decode_stream_ok(x, qweight, qweight.shape[0], bias))
 
 
+def _wo_mxfp4_native_ok(x, qweight, scale, bias=None):
+    """Contract of the decode_gemm_mxfp4 streamer (pure: dtypes, shapes,
+    contiguity, storage offsets -- no CUDA call): bf16 x [..., K] with 1..32
+    rows; qweight uint8 [N, K/2] and scale uint8 exactly [N, K/32], both
+    contiguous and on x's device; K % 128 == 0, 128 <= K <= 2^24; N % 64 == 0;
+    x (as the contiguous [rows, K] the dispatch site passes) and qweight start
+    16-byte aligned, scale 4-byte aligned; bias floating point with N elements
+    (the site casts it)."""
+    import torch
+    if not all(isinstance(t, torch.Tensor) for t in (x, qweight, scale)):
+        return False
+    if not (x.dtype == torch.bfloat16 and x.dim() >= 1
+            and qweight.dtype == torch.uint8 and qweight.dim() == 2
+            and qweight.is_contiguous() and scale.dtype == torch.uint8
+            and scale.is_contiguous()
+            and qweight.device == x.device and scale.device == x.device):
+        return False
+    n, k = qweight.shape[0], 2 * qweight.shape[1]
+    if k < 128 or k % 128 or k > 2 ** 24 or n < 64 or n % 64:
+        return False
+    if tuple(scale.shape) != (n, k // 32):
+        return False
+    if x.shape[-1] != k or not 1 <= x.numel() // k <= 32:
+        return False
+    # a non-contiguous x is copied into a fresh (aligned) allocation
+    if x.is_contiguous() and (x.storage_offset() * 2) % 16:
+        return False
+    if qweight.storage_offset() % 16 or scale.storage_offset() % 4:
+        return False
+    return bias is None or (isinstance(bias, torch.Tensor)
+                            and bias.is_floating_point() and bias.numel() == n)
+
+
+def _wo_mxfp4_linear(x, qweight, scale, bias):
+    import torch
+    from .. import _ext
+    from ..incubate.mx import mx_dequantize
+    n = qweight.shape[0]
+    w = None
+    if x.is_cuda and _ext.use_native(x):
+        C = _ext.get_ext()
+        if _wo_mxfp4_native_ok(x, qweight, scale, bias):
+            b = bias.to(x.dtype).contiguous() if bias is not None else None
+            out = C.decode_gemm_mxfp4(x.reshape(-1, x.shape[-1]).contiguous(),
+                                      qweight, scale, b, 0)
+            return out.reshape(*x.shape[:-1], n)
+        if (x.dtype == torch.bfloat16 and qweight.is_cuda and scale.is_cuda
+                and qweight.dtype == torch.uint8 and scale.dtype == torch.uint8
+                and qweight.dim() == 2 and qweight.is_contiguous()
+                and scale.is_contiguous() and qweight.shape[1] % 16 == 0
+                and tuple(scale.shape) == (n, qweight.shape[1] // 16)
+                and qweight.data_ptr() % 16 == 0):
+            w = C.mx_dequant_fp4(qweight, scale)             # [N, K] bf16
+    if w is None:
+        w = mx_dequantize(qweight, scale).to(x.dtype)
+    return torch.nn.functional.linear(
+        x, w, bias.to(x.dtype) if bias is not None else None)
+
+
 def weight_only_linear(x, qweight, scale, bias=None, weight_dtype="int8",
                        group_size=-1):
     """x [..., K] @ dequant(qweight) + bias.  Decode shapes (<= 32 rows)
-    run the int8 / int4 MFMA W-streaming kernel; int4 prefill shapes
-    dequantize in one dequant_int4 pass; the fallback dequantizes in
-    torch.  int4 operands use the weight_quantize storage format."""
+    run the int8 / int4 / mxfp4 MFMA W-streaming kernel; int4 and mxfp4
+    prefill shapes dequantize in one dequant_int4 / mx_dequant_fp4 pass
+    (mxfp4 then runs F.linear on the N-major weight); the fallback
+    dequantizes in torch.  Operands use the weight_quantize storage format
+    of their dtype."""
     from .. import _ext
     wd = _wo_check(weight_dtype=weight_dtype, group_size=group_size)
     if wd == "int4":
         return _wo_int4_linear(x, qweight, scale, bias, group_size)
+    if wd == "mxfp4":
+        return _wo_mxfp4_linear(x, qweight, scale, bias)
     k, n = qweight.shape
     if (x.is_cuda and _ext.use_native(x)
             and _wo_int8_native_ok(x, qweight, scale, bias)):
@@ -434,9 +510,13 @@ class WeightOnlyLinear(__import__("torch").nn.Module):
         self.register_buffer("qweight", qweight)
         self.register_buffer("scale", scale)
         self.register_buffer("wo_bias", bias)
-        # int4 packs two k rows per byte
-        self.in_features = qweight.shape[0] * (2 if self.weight_dtype == "int4" else 1)
-        self.out_features = qweight.shape[1]
+        if self.weight_dtype == "mxfp4":      # N-major codes [out, in/2]
+            self.in_features = qweight.shape[1] * 2
+            self.out_features = qweight.shape[0]
+        else:
+            # int4 packs two k rows per byte
+            self.in_features = qweight.shape[0] * (2 if self.weight_dtype == "int4" else 1)
+            self.out_features = qweight.shape[1]
 
     @classmethod
     def from_linear(cls, linear, algo="weight_only_int8", group_size=-1):
@@ -459,10 +539,12 @@ def quantize_linears_(model, min_features=1024, skip=("lm_head",),
     """Replace every Linear child of `model` (recursively) whose weight
     is at least [min_features, min_features] with a WeightOnlyLinear --
     int8 weights (~2x less weight memory for serving) or, with
-    algo="weight_only_int4", packed int4 weights (~4x less).  Returns the
-    number of layers converted."""
+    algo="weight_only_int4", packed int4 weights (~4x less), or with
+    algo="weight_only_mxfp4" MXFP4 weights (4.25 bits; layers with
+    in % 128 != 0 or out % 64 != 0 stay as they are).  Returns the number
+    of layers converted."""
     import torch
-    _wo_check(algo=algo, group_size=group_size)
+    mx = _wo_check(algo=algo, group_size=group_size) == "mxfp4"
     n = 0
 
     def walk(mod, prefix=""):
@@ -475,7 +557,8 @@ def quantize_linears_(model, min_features=1024, skip=("lm_head",),
                 continue
             w = getattr(child, "weight", None)
             if (type(child).__name__ == "Linear" and isinstance(w, torch.Tensor)
-                    and w.dim() == 2 and min(w.shape) >= min_features):
+                    and w.dim() == 2 and min(w.shape) >= min_features
+                    and not (mx and (w.shape[0] % 128 or w.shape[1] % 64))):
                 mod._modules[name] = WeightOnlyLinear.from_linear(
                     child, algo=algo, group_size=group_size)
                 n += 1

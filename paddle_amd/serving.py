@@ -298,11 +298,13 @@ class GPTModelRunner:
         self.kv_int8 = kv_cache == "int8"
         if weight_only:
             # weight-only decode: True | "int8" (~2x less weight memory) or
-            # "int4" (~4x less, weight_only_group_size -1 | 64 | 128);
-            # decode linears run the MFMA W-streaming int8 / int4 kernel
-            if weight_only is not True and weight_only not in ("int8", "int4"):
-                raise ValueError("weight_only must be False, True, 'int8' or "
-                                 f"'int4', got {weight_only!r}")
+            # "int4" (~4x less, weight_only_group_size -1 | 64 | 128) or
+            # "mxfp4" (4.25 bits, N-major e2m1 codes with e8m0 block scales);
+            # decode linears run the MFMA W-streaming kernel of the format
+            if weight_only is not True and weight_only not in ("int8", "int4",
+                                                               "mxfp4"):
+                raise ValueError("weight_only must be False, True, 'int8', "
+                                 f"'int4' or 'mxfp4', got {weight_only!r}")
             wdt = "int8" if weight_only is True else weight_only
             from .quantization import quantize_linears_
             quantize_linears_(self.model, skip=("lm_head", "embeddings"),
@@ -698,10 +700,14 @@ class LlamaModelRunner(GPTModelRunner):
                 # entry: (weight dtype, qweight, scale, group size).  int8
                 # [K, N] and packed int4 [K/2, N] both concatenate along n;
                 # per-channel scales are [N], group scales [K/gs, N]
+                # mxfp4 is N-major (codes [N, K/2], scales [N, K/32]): both
+                # concatenate along dim 0
                 wdt, gs = a.q_proj.weight_dtype, a.q_proj.group_size
-                qw = torch.cat([p.qweight for p in projs], dim=1).contiguous()
+                mx = wdt == "mxfp4"
+                qw = torch.cat([p.qweight for p in projs],
+                               dim=0 if mx else 1).contiguous()
                 sc = torch.cat([p.scale for p in projs],
-                               dim=a.q_proj.scale.dim() - 1).contiguous()
+                               dim=0 if mx else a.q_proj.scale.dim() - 1).contiguous()
                 self._qkv_fused.append((wdt, qw, sc, gs))
             elif all(getattr(p, "weight", None) is not None for p in projs):
                 w = torch.cat([p.weight for p in projs], dim=1).contiguous()
@@ -794,7 +800,7 @@ class LlamaModelRunner(GPTModelRunner):
             kind, w, sc, gs = self._qkv_fused[li]
             h2 = h.reshape(B, -1)
             at = layer.self_attn
-            if kind in ("int8", "int4"):
+            if kind in ("int8", "int4", "mxfp4"):
                 from .quantization import weight_only_linear
                 qkv = weight_only_linear(h2, w, sc, weight_dtype=kind,
                                          group_size=gs)
