@@ -1901,8 +1901,11 @@ Tensor amax_abs(const Tensor& x) {
 }
 
 Tensor quant_fp8(const Tensor& x, double scale) {
-  CHECK_IN(x);
-  TORCH_CHECK(x.scalar_type() == torch::kBFloat16 && x.numel() % 8 == 0);
+  TORCH_CHECK(x.is_cuda() && x.is_contiguous(),
+              "quant_fp8: x must be a contiguous GPU tensor");
+  TORCH_CHECK(x.scalar_type() == torch::kBFloat16, "quant_fp8: x must be bfloat16");
+  TORCH_CHECK(x.numel() % 8 == 0, "quant_fp8: numel must be a multiple of 8, got ",
+              x.numel());
   auto out = torch::empty(x.sizes(), x.options().dtype(torch::kFloat8_e4m3fn));
   pa::quant_fp8(x.const_data_ptr(), out.mutable_data_ptr(), (float)scale,
                 x.numel(), cur_stream());

@@ -360,7 +360,16 @@ struct GemmArgs {
 };
 void gemm_bf16(const GemmArgs& g, hipStream_t s);
 void gemm_fp8(const GemmArgs& g, hipStream_t s);
-// bf16 -> e4m3 cast with uniform scale (fused, no fp32 round-trip)
+// bf16 -> e4m3 cast with uniform scale (fused, no fp32 round-trip).  x is
+// contiguous bf16, numel a multiple of 8.  v = fp32(x) * scale is rounded to
+// nearest even, subnormals (down to 2^-9) and the sign of zero included.
+// Out of range, as measured on gfx950 (tests/test_quant_fp8_gpu.py): the
+// conversion rounds first, so 448 < |v| <= 464 gives +-448 (0x7E / 0xFE); from
+// |v| = 480 on, +-Inf included, it gives the NaN byte with v's sign (0x7F /
+// 0xFF), it does NOT saturate; NaN gives a NaN byte.  With scale =
+// fp32(448) / fp32(amax) the largest element is at most one fp32 ulp above
+// 448 and comes out as +-448 for every bf16 amax, so the per-tensor recipe
+// (incubate/fp8.py) needs no clamp; a caller with another scale must clamp.
 void quant_fp8(const void* x, void* out, float scale, int64_t numel,
                hipStream_t s);
 

@@ -4,6 +4,8 @@ fp64 matmul on dequantized operands."""
 import pytest
 import torch
 
+import gemm_ref  # noqa: E402
+
 pytestmark = pytest.mark.gpu
 
 if torch.cuda.is_available():
@@ -116,15 +118,12 @@ def mx_operand(rows, k, seed):
 
 def check_bound(out, a, b, bias, tag):
     """|out - ref| <= 2^-7 |ref| + K 2^-24 sum_k |a_k b_k| (+ 2^-7 |ref| with a
-    bias): the project's rule for a reduced output cast to bf16."""
+    bias): the project's rule for a reduced output cast to bf16 (gemm_ref.py)."""
     ref = a @ b.t()
     if bias is not None:
         ref = ref + bias.double()
-    bound = (2.0 ** -7 * (2 if bias is not None else 1)) * ref.abs() \
-        + a.shape[1] * 2.0 ** -24 * (a.abs() @ b.abs().t())
-    err = (out.double() - ref).abs()
-    print(f"{tag}: worst err/bound {(err / bound.clamp(min=1e-300)).max().item():.3f}")
-    assert bool((err <= bound).all())
+    gemm_ref.check_bound(out, ref, a.abs() @ b.abs().t(), a.shape[1],
+                         roundings=2 if bias is not None else 1, tag=tag)
 
 
 @pytest.mark.parametrize("has_bias", [False, True])
