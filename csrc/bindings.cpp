@@ -1892,6 +1892,154 @@ std::vector<Tensor> moe_combine_bwd(const Tensor& y, const Tensor& dout,
   return {dy, dw};
 }
 
+// ---- dropless MoE: compact route + ragged grouped GEMM -----------------------
+std::vector<Tensor> moe_route_ragged(const Tensor& topi, int64_t num_experts) {
+  const char* op = "moe_route_ragged";
+  moe_check_map(op, "topi", topi, 2);
+  moe_check_tk(op, "topi", topi);
+  TORCH_CHECK(num_experts >= 1 && num_experts <= 65536, op,
+              ": num_experts must be in [1, 65536], got ", num_experts);
+  const int64_t t = topi.size(0), k = topi.size(1);
+  if (t == 0)
+    return {torch::empty({0, k}, topi.options()),
+            torch::empty({0}, topi.options()),
+            torch::zeros({num_experts + 1}, topi.options())};
+  auto slot_of = torch::empty({t, k}, topi.options());
+  auto src_of = torch::empty({t * k}, topi.options());
+  auto offsets = torch::empty({num_experts + 1}, topi.options());
+  pa::moe_route_ragged(topi.const_data_ptr<int>(), slot_of.mutable_data_ptr<int>(),
+                       src_of.mutable_data_ptr<int>(),
+                       offsets.mutable_data_ptr<int>(), t, num_experts, k,
+                       cur_stream());
+  return {slot_of, src_of, offsets};
+}
+
+// Contract of pa::GroupedGemmArgs (kernels/api.h); every check precedes the
+// launch and the allocation and names the op and the operand.
+static void gg_check_mat(const char* op, const char* name, const Tensor& t,
+                         int64_t dim, const Tensor& dev_of) {
+  TORCH_CHECK(t.is_cuda() && t.device() == dev_of.device(), op, ": ", name,
+              " must be on the GPU of a");
+  TORCH_CHECK(t.scalar_type() == torch::kBFloat16, op, ": ", name,
+              " must be bfloat16, got ", t.scalar_type());
+  TORCH_CHECK(t.dim() == dim, op, ": ", name, " must have rank ", dim, ", got ",
+              t.dim());
+  TORCH_CHECK(t.stride(dim - 1) == 1 || t.size(dim - 1) == 1, op, ": ", name,
+              " must have unit inner stride");
+  for (int64_t i = 0; i + 1 < dim; ++i)
+    TORCH_CHECK(t.stride(i) % 8 == 0 && t.stride(i) >= 0, op, ": ", name,
+                " strides must be multiples of 8 elements (16 bytes), got ",
+                t.stride(i));
+  TORCH_CHECK(aligned16(t), op, ": ", name, " data must be 16-byte aligned");
+}
+
+static void gg_check_dim(const char* op, const char* name, int64_t v) {
+  TORCH_CHECK(v >= 64 && v % 64 == 0 && v < (1LL << 31), op, ": ", name,
+              " must be a multiple of 64 and >= 64, got ", v);
+}
+
+static int64_t gg_check_offsets(const char* op, const Tensor& offsets,
+                                const Tensor& a) {
+  moe_check_map(op, "offsets", offsets, 1);
+  TORCH_CHECK(offsets.device() == a.device(), op,
+              ": offsets must be on the GPU of a");
+  const int64_t e = offsets.size(0) - 1;
+  TORCH_CHECK(e >= 1 && e <= 1024, op,
+              ": offsets must have E + 1 entries with 1 <= E <= 1024, got ",
+              offsets.size(0));
+  return e;
+}
+
+// offsets int32 [E + 1] -> tile map int32 [grouped_gemm_map_tiles(rows, E), 2]
+Tensor grouped_gemm_plan(const Tensor& offsets, int64_t rows) {
+  const char* op = "grouped_gemm_plan";
+  moe_check_map(op, "offsets", offsets, 1);
+  const int64_t e = offsets.size(0) - 1;
+  TORCH_CHECK(e >= 1 && e <= 1024, op,
+              ": offsets must have E + 1 entries with 1 <= E <= 1024, got ",
+              offsets.size(0));
+  TORCH_CHECK(rows >= 0 && rows < (1LL << 31), op,
+              ": rows must be in [0, 2^31), got ", rows);
+  const int64_t tiles = pa::grouped_gemm_map_tiles(rows, e);
+  if (rows == 0) return torch::full({tiles, 2}, -1, offsets.options());
+  auto map = torch::empty({tiles, 2}, offsets.options());
+  pa::grouped_gemm_plan(offsets.const_data_ptr<int>(), map.mutable_data_ptr<int>(),
+                        rows, e, cur_stream());
+  return map;
+}
+
+// form 0 NN | 1 NT | 2 TN (pa::GroupedForm); tile_map: NN / NT, from
+// grouped_gemm_plan over the same offsets
+Tensor grouped_gemm_bf16(const Tensor& a, const Tensor& b, const Tensor& offsets,
+                         const c10::optional<Tensor>& tile_map, int64_t form,
+                         const c10::optional<Tensor>& bias) {
+  const char* op = "grouped_gemm_bf16";
+  TORCH_CHECK(form >= 0 && form <= 2, op, ": form must be 0 (NN), 1 (NT) or 2 "
+              "(TN), got ", form);
+  const bool tn = form == pa::kGroupedTN;
+  gg_check_mat(op, "a", a, 2, a);
+  gg_check_mat(op, "b", b, tn ? 2 : 3, a);
+  const int64_t e = gg_check_offsets(op, offsets, a);
+  const int64_t rows = a.size(0);
+  TORCH_CHECK(rows < (1LL << 31), op, ": a needs R < 2^31 rows, got ", rows);
+  pa::GroupedGemmArgs g{};
+  g.rows = rows; g.groups = e; g.form = (int)form;
+  g.lda = a.stride(0);
+  std::vector<int64_t> out_shape;
+  if (tn) {
+    TORCH_CHECK(b.size(0) == rows, op, ": b must have the R = ", rows,
+                " rows of a, got ", b.size(0));
+    TORCH_CHECK(!bias.has_value(), op, ": bias is taken by the NN form only");
+    g.m = a.size(1); g.n = b.size(1);
+    gg_check_dim(op, "a columns (M)", g.m);
+    gg_check_dim(op, "b columns (N)", g.n);
+    g.ldb = b.stride(0);
+    g.ldc = g.n; g.c_gs = g.m * g.n;
+    TORCH_CHECK(e * ((g.m + 127) / 128) * ((g.n + 127) / 128) < (1LL << 31), op,
+                ": a / b give too many output tiles");
+    out_shape = {e, g.m, g.n};
+  } else {
+    const bool nn = form == pa::kGroupedNN;
+    g.k = a.size(1);
+    g.n = b.size(nn ? 2 : 1);
+    TORCH_CHECK(b.size(0) == e, op, ": b must have E = ", e,
+                " groups like offsets, got ", b.size(0));
+    TORCH_CHECK(b.size(nn ? 1 : 2) == g.k, op, ": b must have the K = ", g.k,
+                " of a, got ", b.size(nn ? 1 : 2));
+    gg_check_dim(op, "a columns (K)", g.k);
+    gg_check_dim(op, "b columns (N)", g.n);
+    g.ldb = b.stride(1); g.b_gs = b.stride(0);
+    g.ldc = g.n;
+    if (bias.has_value()) {
+      TORCH_CHECK(nn, op, ": bias is taken by the NN form only");
+      gg_check_mat(op, "bias", *bias, 2, a);
+      TORCH_CHECK(bias->size(0) == e && bias->size(1) == g.n, op,
+                  ": bias must be [E, N] = [", e, ", ", g.n, "]");
+      g.bias = bias->const_data_ptr();
+      g.ldbias = bias->stride(0);
+    }
+    const int64_t tiles = pa::grouped_gemm_map_tiles(rows, e);
+    TORCH_CHECK(tile_map.has_value(), op, ": tile_map is required by NN / NT");
+    moe_check_map(op, "tile_map", *tile_map, 2);
+    TORCH_CHECK(tile_map->device() == a.device() && tile_map->size(0) == tiles &&
+                tile_map->size(1) == 2, op, ": tile_map must be [", tiles,
+                ", 2] on the GPU of a (grouped_gemm_plan of these offsets and "
+                "rows)");
+    TORCH_CHECK(tiles * ((g.n + 127) / 128) < (1LL << 31), op,
+                ": a / b give too many output tiles");
+    g.tile_map = tile_map->const_data_ptr<int>();
+    out_shape = {rows, g.n};
+  }
+  if (rows == 0)
+    return torch::zeros(out_shape, a.options());
+  auto c = torch::empty(out_shape, a.options());
+  g.a = a.const_data_ptr(); g.b = b.const_data_ptr();
+  g.c = c.mutable_data_ptr();
+  g.offsets = offsets.const_data_ptr<int>();
+  pa::grouped_gemm_bf16(g, cur_stream());
+  return c;
+}
+
 Tensor amax_abs(const Tensor& x) {
   CHECK_IN(x);
   auto out = torch::zeros({}, x.options().dtype(torch::kFloat));
@@ -2004,6 +2152,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("moe_combine", &moe_combine, py::arg("y"), py::arg("w"),
         py::arg("slot_of"));
   m.def("moe_combine_bwd", &moe_combine_bwd);
+  m.def("moe_route_ragged", &moe_route_ragged, py::arg("topi"),
+        py::arg("num_experts"));
+  m.def("grouped_gemm_plan", &grouped_gemm_plan, py::arg("offsets"),
+        py::arg("rows"));
+  m.def("grouped_gemm_bf16", &grouped_gemm_bf16, py::arg("a"), py::arg("b"),
+        py::arg("offsets"), py::arg("tile_map"), py::arg("form"),
+        py::arg("bias") = c10::nullopt);
   m.def("gemm_fp8_nt", &gemm_fp8_nt, py::arg("a"), py::arg("bt"),
         py::arg("scale_ab") = 1.0, py::arg("bias") = c10::nullopt);
   m.def("gemm_fp8_nt_batched", &gemm_fp8_nt_batched, py::arg("a"),

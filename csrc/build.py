@@ -30,6 +30,7 @@ HIP_EXTRA = {
     "flashmask": _NO_PK_F32,
     "gemm_mx": _NO_PK_F32,
     "decode_gemm_mx": _NO_PK_F32,
+    "grouped_gemm": _NO_PK_F32,
 }
 
 

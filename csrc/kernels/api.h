@@ -512,4 +512,56 @@ void moe_dispatch(const MoePermuteArgs& a, hipStream_t s);
 void moe_combine(const MoePermuteArgs& a, hipStream_t s);
 void moe_combine_bwd(const MoePermuteArgs& a, hipStream_t s);
 
+// ---- dropless MoE: compact route + ragged grouped GEMM ------------------------
+// moe_route_ragged (moe.hip): topi int32 [T, K] -> slot_of [T, K], src_of
+// [T * K], offsets [E + 1], all int32 and all written in full by the kernel.
+// pos(t, kk) as in moe_route; offsets[e] = number of valid ids below e (the
+// exclusive prefix sum of the per-expert counts), offsets[E] = number of valid
+// entries; slot_of[t, kk] = offsets[e] + pos, nothing is dropped;
+// src_of[slot] = t * K + kk; an id outside [0, E) gets slot -1 and the rows
+// [offsets[E], T * K) of src_of are -1.  No atomics, no host read.
+void moe_route_ragged(const int* topi, int* slot_of, int* src_of, int* offsets,
+                      int64_t t, int64_t e, int64_t k, hipStream_t s);
+
+// grouped_gemm_bf16 (grouped_gemm.hip): bf16 in, fp32 accumulate, bf16 out over
+// `rows` = R rows sorted by group; group e owns rows [offsets[e], offsets[e+1]),
+// read on the device.
+//   kGroupedNN  C[r, :] = A[r, :] . B[g(r)] (+ bias[g(r), :])
+//               A [R, k], B [E, k, n] (b_gs, ldb), bias [E, n] (ldbias), C [R, n]
+//   kGroupedNT  C[r, :] = A[r, :] . B[g(r)]^T     A [R, k], B [E, n, k], C [R, n]
+//   kGroupedTN  C[e] = sum_{r in e} A[r, :]^T (x) B[r, :]
+//               A [R, m], B [R, n], C [E, m, n] (c_gs, ldc); an empty group
+//               gives zeros; one block sums a group in row order, no atomics
+// NN / NT take the tile map that grouped_gemm_plan wrote from the same
+// offsets: grouped_gemm_map_tiles(R, E) int32 pairs (group, first row), one
+// launch, every element written; one map serves every NN / NT call of a route.
+// Rows [offsets[E], R) of an NN / NT output are written as zeros; every output
+// element is written, outputs need no initialisation.
+// Contract (checked by the binding before any launch or allocation):
+//   * everything on one GPU; a, b, c, bias bf16 with unit inner stride,
+//     16-byte aligned bases, row strides and group strides;
+//   * k, n, m multiples of 64 and >= 64; 1 <= E <= 1024; R < 2^31;
+//   * offsets int32 contiguous [E + 1]; tile_map int32 contiguous
+//     [grouped_gemm_map_tiles(R, E), 2];
+//   * R == 0 launches nothing.
+// Offsets are not trusted: group e covers [clamp(o_e), clamp(max(o_e+1, o_e)))
+// with clamp to [0, R]; malformed offsets or a foreign map give an
+// unspecified but memory-safe result.
+constexpr int kGroupedGemmBM = 128;
+enum GroupedForm : int { kGroupedNN = 0, kGroupedNT = 1, kGroupedTN = 2 };
+struct GroupedGemmArgs {
+  const void *a, *b;
+  void* c;
+  const void* bias;                    // NN only, may be null
+  const int *offsets, *tile_map;       // tile_map: NN / NT
+  int64_t rows, groups, m, n, k;
+  int64_t lda, ldb, ldc, ldbias;
+  int64_t b_gs, c_gs;                  // group strides of B (NN / NT), C (TN)
+  int form;
+};
+int64_t grouped_gemm_map_tiles(int64_t rows, int64_t groups);
+void grouped_gemm_plan(const int* offsets, int* tile_map, int64_t rows,
+                       int64_t groups, hipStream_t s);
+void grouped_gemm_bf16(const GroupedGemmArgs& a, hipStream_t s);
+
 }  // namespace pa

@@ -135,6 +135,78 @@ __global__ __launch_bounds__(NW * 64) void moe_route_kernel(
   if (threadIdx.x == 0) counts[e] = n_e;
 }
 
+// Compact (dropless) route: topi [T, K] -> slot_of [T, K], src_of [T * K],
+// offsets [E + 1], every element written by plain stores.  Block e walks the
+// same sequence as moe_route_kernel twice.  The first walk counts, per wave
+// run, the entries of expert e, the valid entries below e and all valid
+// entries: topi is L2-resident, so each block forms its own prefix over the
+// experts before it and no second launch or atomic is needed.  The second
+// walk hands out offsets[e] + pos.  All blocks share the -1 tail of src_of.
+template <int NW>
+__global__ __launch_bounds__(NW * 64) void moe_route_ragged_kernel(
+    const int* __restrict__ topi, int* __restrict__ slot_of,
+    int* __restrict__ src_of, int* __restrict__ offsets, int T, int E, int K) {
+  __shared__ int wmine[NW], wbelow[NW], wvalid[NW];
+  const int e = blockIdx.x;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int nch = (T + 63) >> 6;
+  const int total = nch * K;
+  const int per = (total + NW - 1) / NW;
+  const int c0 = min(total, wv * per), c1 = min(total, c0 + per);
+  const unsigned long long lower = (1ull << lane) - 1;
+  int nm = 0, nb = 0, nv = 0;
+  for (int c = c0; c < c1; ++c) {
+    const int kk = c / nch, t = ((c - kk * nch) << 6) + lane;
+    const int id = (t < T) ? topi[t * K + kk] : -1;
+    nm += __popcll(__ballot(id == e));
+    nb += __popcll(__ballot((unsigned)id < (unsigned)e));
+    nv += __popcll(__ballot((unsigned)id < (unsigned)E));
+  }
+  if (lane == 0) { wmine[wv] = nm; wbelow[wv] = nb; wvalid[wv] = nv; }
+  __syncthreads();
+  int base = 0, below = 0, valid = 0;
+#pragma unroll
+  for (int i = 0; i < NW; ++i) {
+    if (i < wv) base += wmine[i];
+    below += wbelow[i];
+    valid += wvalid[i];
+  }
+  base += below;
+  for (int c = c0; c < c1; ++c) {
+    const int kk = c / nch, t = ((c - kk * nch) << 6) + lane;
+    const int id = (t < T) ? topi[t * K + kk] : e;
+    const bool match = (t < T) && id == e;
+    const unsigned long long mask = __ballot(match);
+    if (match) {
+      const int slot = base + __popcll(mask & lower);
+      slot_of[t * K + kk] = slot;
+      src_of[slot] = t * K + kk;
+    }
+    if (e == 0 && t < T && (unsigned)id >= (unsigned)E) slot_of[t * K + kk] = -1;
+    base += __popcll(mask);
+  }
+  for (long long p = valid + (long long)e * NW * 64 + threadIdx.x; p < (long long)T * K;
+       p += (long long)E * NW * 64)
+    src_of[p] = -1;
+  if (threadIdx.x == 0) {
+    offsets[e] = below;
+    if (e == E - 1) offsets[E] = valid;
+  }
+}
+
+void moe_route_ragged(const int* topi, int* slot_of, int* src_of, int* offsets,
+                      int64_t t, int64_t e, int64_t k, hipStream_t s) {
+  const int64_t chunks = ((t + 63) / 64) * k;
+  auto go = [&](auto NW) {
+    hipLaunchKernelGGL((moe_route_ragged_kernel<NW()>), dim3((unsigned)e),
+                       dim3(NW() * 64), 0, s, topi, slot_of, src_of, offsets,
+                       (int)t, (int)e, (int)k);
+  };
+  if (chunks <= 4) go(std::integral_constant<int, 1>{});
+  else if (chunks <= 64) go(std::integral_constant<int, 4>{});
+  else go(std::integral_constant<int, 16>{});
+}
+
 void moe_gate_topk(const float* logits, float* topv, int* topi, float* me,
                    float* ce, int64_t t, int64_t e, int64_t k, hipStream_t s) {
   long long waves = t;

@@ -185,18 +185,29 @@ class MoELayer(nn.Layer):
     (ops/functional.py) -- slots unique across k in GShard order, fp32 gate
     weights, one rounding in the combine, no Python loop over k and no host
     read.  The two modes drop different tokens at k >= 2, so their results
-    differ."""
+    differ.  dispatch="dropless": moe_route_ragged packs the T * k entries by
+    expert with no capacity, so no token is dropped and no padding row is
+    computed; the experts run as ragged grouped GEMMs (hot.ragged_ffn) over
+    device-side offsets.  Single rank and grouped experts only.  The kernels
+    and the no-host-read property hold on the grouped GEMM contract alone
+    (bf16 operands, h and I multiples of 64, not under tracing): off it, e.g.
+    with fp32 weights, hot.ragged_ffn runs the torch spec, which reads the
+    offsets on the host and so cannot be graph-captured."""
 
     def __init__(self, hidden_size, inter_size, num_experts, k=2,
                  capacity_factor=2.0, ep_group=None, grouped=True,
                  dispatch="index"):
         super().__init__()
-        if dispatch not in ("index", "fused"):
-            raise ValueError(f"MoELayer: dispatch must be 'index' or 'fused', "
-                             f"got {dispatch!r}")
+        if dispatch not in ("index", "fused", "dropless"):
+            raise ValueError(f"MoELayer: dispatch must be 'index', 'fused' or "
+                             f"'dropless', got {dispatch!r}")
         self.dispatch = dispatch
         self.ep_group = ep_group
         self.ep_size = ep_group.nranks if ep_group else 1
+        if dispatch == "dropless" and (self.ep_size > 1 or not grouped):
+            raise ValueError("MoELayer: dispatch='dropless' needs ep_size == 1 "
+                             "(a variable-size all-to-all needs host-side "
+                             "sizes) and grouped=True")
         assert num_experts % self.ep_size == 0
         self.num_experts = num_experts
         self.local_experts = num_experts // self.ep_size
@@ -217,6 +228,14 @@ class MoELayer(nn.Layer):
         T = tokens.shape[0]
         topv, topi, aux = self.gate(tokens)
         self.aux_loss = aux
+        if self.dispatch == "dropless":
+            ex = self.experts
+            slot_of, src_of, offsets = hot.moe_route_ragged(topi, self.num_experts)
+            rows = hot.moe_dispatch(tokens, src_of, slot_of)
+            back = hot.ragged_ffn(rows, ex.w1, ex.b1, ex.w2, ex.b2, offsets,
+                                  topi, src_of)
+            out = hot.moe_combine(back, topv.float(), slot_of, src_of)
+            return out.view(b, s, h)
         cap = int(self.capacity_factor * T * self.k / self.num_experts) + 1
         cap = max(cap, 4)
         if self.dispatch == "fused":

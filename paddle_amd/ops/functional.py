@@ -1899,6 +1899,177 @@ def moe_combine(y, w, slot_of, src_of):
 
 
 # ---------------------------------------------------------------------------
+# Dropless MoE: compact route + ragged grouped GEMM (csrc/kernels/moe.hip
+# moe_route_ragged, grouped_gemm.hip; docs/KERNELS.md "ragged grouped GEMM").
+# The torch paths are the executable spec; the grouped GEMM's one reads its
+# offsets on the host and is the CPU / off-contract path only.
+# ---------------------------------------------------------------------------
+def moe_route_ragged(topi, num_experts):
+    """topi integer [T, K] -> (slot_of [T, K], src_of [T * K], offsets
+    [E + 1]), int32.  pos(t, kk) as in moe_route; offsets is the exclusive
+    prefix sum of the per-expert counts of valid ids, offsets[E] their number;
+    slot_of = offsets[e] + pos, nothing is dropped; src_of[slot] = t * K + kk.
+    An id outside [0, E) gets slot -1 and is counted nowhere; the rows
+    [offsets[E], T * K) of src_of are -1."""
+    E = int(num_experts)
+    if _ext.use_native(topi):
+        return tuple(_ext.get_ext().moe_route_ragged(
+            topi.to(torch.int32).contiguous(), E))
+    if topi.dim() != 2 or not 1 <= topi.shape[1] <= 8 or E < 1:
+        raise ValueError("moe_route_ragged: topi must be [T, K] with "
+                         "1 <= K <= 8 and num_experts >= 1")
+    T, K = topi.shape
+    dev = topi.device
+    ids = topi.t().reshape(-1).long()                  # sequence i = kk * T + t
+    ok = (ids >= 0) & (ids < E)
+    key = torch.where(ok, ids, torch.full_like(ids, E))
+    counts = torch.zeros(E + 1, dtype=torch.long, device=dev).scatter_add_(
+        0, key, torch.ones_like(key))
+    order = torch.argsort(key, stable=True)            # valid entries by slot
+    offsets = torch.cat([counts.new_zeros(1), counts[:E].cumsum(0)])
+    i = torch.arange(K * T, device=dev)
+    src = (i % max(T, 1)) * K + i // max(T, 1)
+    in_range = i < offsets[E]
+    src_of = torch.where(in_range, src[order], torch.full_like(src, -1))
+    slot = torch.empty_like(ids)
+    slot[order] = torch.where(in_range, i, torch.full_like(i, -1))
+    return (slot.view(K, T).t().contiguous().to(torch.int32),
+            src_of.to(torch.int32), offsets.to(torch.int32))
+
+
+_GG_FORMS = {"nn": 0, "nt": 1, "tn": 2}
+
+
+def _gg_mat_ok(t, dim):
+    return (t.dtype == torch.bfloat16 and t.dim() == dim and t.stride(-1) == 1
+            and all(s % 8 == 0 for s in t.stride()[:-1])
+            and t.data_ptr() % 16 == 0)
+
+
+def _grouped_gemm_native_ok(a, b, offsets, form, bias=None):
+    """Contract of csrc/kernels/api.h GroupedGemmArgs; the binding checks it
+    again and raises."""
+    if not (_ext.use_native(a) and form in _GG_FORMS
+            and b.device == a.device and offsets.device == a.device
+            and offsets.dtype == torch.int32 and offsets.dim() == 1
+            and offsets.is_contiguous() and 2 <= offsets.shape[0] <= 1025
+            and _gg_mat_ok(a, 2) and _gg_mat_ok(b, 2 if form == "tn" else 3)):
+        return False
+    if bias is not None and not (form == "nn" and bias.device == a.device
+                                 and _gg_mat_ok(bias, 2)):
+        return False
+    dims = list(a.shape[1:]) + list(b.shape[1:])
+    return all(d >= 64 and d % 64 == 0 for d in dims)
+
+
+def grouped_gemm_plan(offsets, rows):
+    """offsets int32 [E + 1] -> the tile map of the NN / NT forms for `rows`
+    rows; one launch per route, shared by every NN / NT call over it."""
+    return _ext.get_ext().grouped_gemm_plan(offsets, int(rows))
+
+
+def grouped_gemm(a, b, offsets, form, bias=None, plan=None):
+    """Ragged grouped GEMM over R rows sorted by group; group e owns the rows
+    [offsets[e], offsets[e + 1]).
+      "nn": out[r] = a[r] @ b[g(r)] (+ bias[g(r)])   a [R, K], b [E, K, N]
+      "nt": out[r] = a[r] @ b[g(r)].T                a [R, K], b [E, N, K]
+      "tn": out[e] = a[rows of e].T @ b[rows of e]   a [R, M], b [R, N]
+    Rows at or past offsets[E] give zeros (nn, nt) and take no part (tn); an
+    empty group of "tn" gives zeros.  fp32 accumulation, output in a's dtype.
+    plan: grouped_gemm_plan(offsets, R), made here when absent."""
+    if form not in _GG_FORMS:
+        raise ValueError(f"grouped_gemm: form must be 'nn', 'nt' or 'tn', got {form!r}")
+    if _grouped_gemm_native_ok(a, b, offsets, form, bias):
+        C = _ext.get_ext()
+        if plan is None and form != "tn":
+            plan = C.grouped_gemm_plan(offsets, a.shape[0])
+        return C.grouped_gemm_bf16(a, b, offsets, plan, _GG_FORMS[form], bias)
+    E = offsets.shape[0] - 1
+    R = a.shape[0]
+    off = [min(max(int(o), 0), R) for o in offsets.tolist()]
+    acc = torch.promote_types(a.dtype, torch.float32)
+    parts = []
+    for e in range(E):
+        lo, hi = off[e], max(off[e], off[e + 1])
+        ae = a[lo:hi].to(acc)
+        if form == "tn":
+            parts.append(ae.t() @ b[lo:hi].to(acc))
+            continue
+        be = b[e].to(acc)
+        ce = ae @ (be if form == "nn" else be.t())
+        parts.append(ce + bias[e].to(acc) if bias is not None else ce)
+    if form == "tn":
+        return torch.stack(parts).to(a.dtype)
+    used = sum(p.shape[0] for p in parts)
+    parts.append(a.new_zeros(max(R - used, 0), parts[0].shape[1], dtype=acc))
+    return torch.cat(parts)[:R].to(a.dtype)
+
+
+class _RaggedFFN(torch.autograd.Function):
+    """Expert FFN over compact rows, on the grouped GEMM kernels only: the
+    stored w1 [E, h, I] / w2 [E, I, h] serve forward (NN), dgrad (NT) and
+    wgrad (TN) in place.  row_expert int64 [R]: expert of each row, E for a
+    row of the invalid tail."""
+
+    @staticmethod
+    def forward(ctx, x, w1, b1, w2, b2, offsets, plan, row_expert):
+        C = _ext.get_ext()
+        z = C.grouped_gemm_bf16(x, w1, offsets, plan, 0, b1)
+        g = C.bias_gelu_fwd(z, None)
+        out = C.grouped_gemm_bf16(g, w2, offsets, plan, 0, b2)
+        ctx.save_for_backward(x, z, g, w1, w2, offsets, plan, row_expert)
+        return out
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, z, g, w1, w2, offsets, plan, row_expert = ctx.saved_tensors
+        C = _ext.get_ext()
+        E = w1.shape[0]
+        dy = dy.contiguous()
+        need_x, need_w1, need_b1, need_w2, need_b2 = ctx.needs_input_grad[:5]
+
+        def colsums(rows):
+            s = torch.zeros(E + 1, rows.shape[1], dtype=torch.float32,
+                            device=rows.device)
+            return s.index_add_(0, row_expert, rows.float())[:E].to(rows.dtype)
+
+        dx = dw1 = db1 = None
+        if need_x or need_w1 or need_b1:
+            dg = C.grouped_gemm_bf16(dy, w2, offsets, plan, 1, None)
+            dz = C.bias_gelu_bwd(dg, z, None)
+            if need_x:
+                dx = C.grouped_gemm_bf16(dz, w1, offsets, plan, 1, None)
+            if need_w1:
+                dw1 = C.grouped_gemm_bf16(x, dz, offsets, None, 2, None)
+            if need_b1:
+                db1 = colsums(dz)
+        dw2 = C.grouped_gemm_bf16(g, dy, offsets, None, 2, None) if need_w2 else None
+        db2 = colsums(dy) if need_b2 else None
+        return dx, dw1, db1, dw2, db2, None, None, None
+
+
+def ragged_ffn(x, w1, b1, w2, b2, offsets, topi, src_of):
+    """out[r] = gelu(x[r] @ w1[e] + b1[e]) @ w2[e] + b2[e] for the expert e of
+    compact row r (moe_route_ragged order), zeros on the invalid tail.  x
+    [R, h], w1 [E, h, I], b1 [E, I], w2 [E, I, h], b2 [E, h].  Native when the
+    grouped GEMM contract holds for every operand, else the torch spec."""
+    if (_grouped_gemm_native_ok(x, w1, offsets, "nn", b1)
+            and _grouped_gemm_native_ok(x, w2, offsets, "nt")
+            and b2.device == x.device and _gg_mat_ok(b2, 2) and x.shape[0] > 0
+            and not _tracing()):
+        E = w1.shape[0]
+        ids = topi.reshape(-1).long()
+        src = src_of.long()
+        row_expert = torch.where(src >= 0, ids[src.clamp(min=0)],
+                                 torch.full_like(src, E)).clamp(0, E)
+        plan = _ext.get_ext().grouped_gemm_plan(offsets, x.shape[0])
+        return _RaggedFFN.apply(x.contiguous(), w1, b1, w2, b2, offsets, plan,
+                                row_expert)
+    z = grouped_gemm(x, w1, offsets, "nn", b1)
+    return grouped_gemm(bias_gelu(z, None), w2, offsets, "nn", b2)
+
+
+# ---------------------------------------------------------------------------
 # fused FFN: fc1(+bias+GELU in the hipBLASLt epilogue) -> fc2.
 # Backward folds dGELU + fc1 bias-grad into fc2's dgrad GEMM (DGELU_BGRAD),
 # so the [tokens, 4h] activation is never touched by a separate elementwise

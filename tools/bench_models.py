@@ -67,7 +67,8 @@ def main():
     if len(sys.argv) > 1:
         import argparse
         ap = argparse.ArgumentParser()
-        ap.add_argument("--moe-dispatch", choices=("index", "fused"), required=True,
+        ap.add_argument("--moe-dispatch", choices=("index", "fused", "dropless"),
+                        required=True,
                         help="run only the GPT-MoE config with this MoELayer dispatch")
         return bench_moe(ap.parse_args().moe_dispatch)
     torch.manual_seed(0)

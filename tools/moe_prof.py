@@ -1,6 +1,7 @@
 """fp8 vs bf16 grouped-expert FFN microbench (config-5 shapes).
---layer index|fused: one MoELayer forward+backward instead (T 8192, h 1024,
-E 64, k 2, bf16) with that dispatch mode; --route: moe_route block forms."""
+--layer index|fused|dropless: one MoELayer forward+backward instead (T 8192,
+h 1024, E 64, k 2, bf16) with that dispatch mode, and its peak memory;
+--route: moe_route block forms."""
 import sys, os, time, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import paddle_amd as paddle
@@ -22,8 +23,9 @@ def layer_bench(mode):
                     requires_grad=True)
     def fb():
         (layer(x).float().sum() + layer.aux_loss).backward()
-    print(f"MoELayer f+b T8192 h1024 E64 k2 dispatch={mode}: "
-          f"{bench(fb, 20):.3f} ms", flush=True)
+    ms = bench(fb, 20)
+    print(f"MoELayer f+b T8192 h1024 E64 k2 dispatch={mode}: {ms:.3f} ms, "
+          f"peak {torch.cuda.max_memory_allocated() / 2 ** 20:.0f} MiB", flush=True)
 
 def route_bench():
     C = paddle._ext.get_ext()
